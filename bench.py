@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — driver-contract benchmark of the MI355X Halo2/Pasta backend.
 
-`python bench.py --gpus N --steps K --warmup W [--workload msm|ntt]`
+`python bench.py --gpus N --steps K --warmup W [--workload msm|ntt]
+                 [--dump-outputs DIR] [--full]`
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+`--dump-outputs DIR` also writes what the last timed step returned to its
+caller as DIR/<name>.npy (float32; one value per output byte, so two builds
+compare exactly). `--full` adds the legs that take runs of their own: the
+uncontended roofline probe and the CPU-oracle baseline (`roofline` and
+`cpu_baseline` are null in the result line without it).
 
 A "step" is one pass of the hot path over one batch of synthetic input.
 Round-1 workload: BASELINE.json configs[1] — the 2^20-point Pallas-family
@@ -46,6 +54,10 @@ os.environ.setdefault("OMP_WAIT_POLICY", "PASSIVE")
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
+# the h-fold kernels that build() pre-compiled sit next to the circuit
+# descs; the library looks for them relative to the working directory, so
+# pin the place (a miss costs minutes of runtime compilation at keygen)
+os.environ.setdefault("TG_HF_CACHE", os.path.join(REPO, "tests", "golden"))
 
 import numpy as np  # noqa: E402
 
@@ -142,7 +154,17 @@ def main():
     ap.add_argument("--streams", type=int, default=0,
                     help="concurrent proving contexts per GPU (proof workload); "
                          "0 = auto, scaled to this rank's CPU share")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the uncontended roofline probe and the "
+                         "CPU-oracle baseline (untimed legs of their own)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+
+    # name -> bytes the last step handed back to its caller (--dump-outputs)
+    last_out = {}
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -213,6 +235,7 @@ def main():
         comp_units, rl_units = _make_ptx_units(rank)
         import ctypes as _ct
         lib = taiga_amd.api.load_library()
+        unit_out = [None] * C  # per context: what its latest unit returned
 
         if args.workload == "ptx":
             bufs = [_ct.create_string_buffer(1 << 18) for _ in range(C)]
@@ -224,11 +247,12 @@ def main():
                                       2, 2, rl_units, rng_s, bufs[j],
                                       len(bufs[j]), _ct.byref(out_len))
                 assert rc == 0, f"tg_ptx_build rc={rc}"
+                unit_out[j] = out_len.value
         else:
 
             def one_unit(j, i):
                 rng_s = (SEED + 99 + rank).to_bytes(16, "little") + i.to_bytes(16, "little")
-                ctxs[j].compliance_prove(comp_units[:1528], rng_s)
+                unit_out[j] = ctxs[j].compliance_prove(comp_units[:1528], rng_s)
 
         def step():
             base = counter[0]
@@ -236,6 +260,13 @@ def main():
             futs = [pool.submit(one_unit, j, base + j) for j in range(C)]
             for f in futs:
                 f.result()
+
+        def collect():
+            for j in range(C):
+                if args.workload == "ptx":
+                    last_out[f"ptx_bundle_ctx{j}"] = bufs[j].raw[:unit_out[j]]
+                else:
+                    last_out[f"proof_ctx{j}"], last_out[f"instance_ctx{j}"] = unit_out[j]
     elif args.workload == "verify":
         # batch verification: a step = one tg_verify_batch of
         # a 6-proof bundle (a shielded ptx carries 2 compliance + 4 RL
@@ -256,15 +287,25 @@ def main():
             proof, inst = gpu.compliance_prove(comp_units[(i % 2) * 1528:(i % 2 + 1) * 1528], rng_s)
             items.append((inst, proof))
 
+        unit_out = [None]
+
         def step():
-            assert gpu.verify_batch_raw(items)
+            unit_out[0] = gpu.verify_batch_raw(items)
+            assert unit_out[0]
+
+        def collect():
+            last_out["batch_accepted"] = bytes([1 if unit_out[0] else 0])
     elif args.workload == "msm":
         gpu.gen_bases(MSM_N, SEED)  # same base set on every rank
         scalars = gen_scalars(MSM_N, SEED + 1000 + rank)  # per-rank scalars
         gpu.scalars_upload(scalars)
+        unit_out = [None]
 
         def step():
-            gpu.msm_resident(MSM_N, base_set=0)
+            unit_out[0] = gpu.msm_resident(MSM_N, base_set=0)
+
+        def collect():
+            last_out["msm_point_xy"] = unit_out[0]
     else:
         n = 1 << NTT_K
         poly = gen_scalars(n, SEED + 2000 + rank)
@@ -273,6 +314,15 @@ def main():
         def step():
             gpu.ntt_resident(NTT_K, inverse=False)
             gpu.ntt_resident(NTT_K, inverse=True)
+
+        def collect():
+            # the resident polynomial is 128 MB: keep a fixed seeded sample
+            # of 2^16 elements (32 B each)
+            rows = np.random.Generator(np.random.Philox(SEED + 7000)).choice(
+                n, size=1 << 16, replace=False)
+            rows.sort()
+            whole = np.frombuffer(gpu.poly_download(NTT_K), dtype=np.uint8)
+            last_out["ntt_poly_sample"] = whole.reshape(n, 32)[rows].tobytes()
 
     # ---- warmup ----
     for _ in range(args.warmup):
@@ -297,6 +347,16 @@ def main():
     barrier_sync()
     elapsed = time.perf_counter() - t0
 
+    # ---- --dump-outputs: what the last timed step returned, one float32
+    # per output byte (exact), before any later leg reuses the buffers ----
+    if args.dump_outputs:
+        collect()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = f"_rank{rank}" if world > 1 else ""
+        for nm, raw in last_out.items():
+            np.save(os.path.join(args.dump_outputs, f"{nm}{sfx}.npy"),
+                    np.frombuffer(raw, dtype=np.uint8).astype(np.float32))
+
     # max over ranks
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -307,8 +367,9 @@ def main():
     # For the concurrent proof workloads, the timed region's per-launch
     # averages are stretched by C contexts time-sharing the chip; re-run
     # ONE unit uncontended with fresh counters so the roofline reflects
-    # kernel quality, not contention (VERDICT round-1 item).
-    if args.workload in ("ptx", "proof") and rank == 0:
+    # kernel quality, not contention (VERDICT round-1 item). The probe is
+    # a run of its own, so the roofline is a --full leg on every workload.
+    if args.full and args.workload in ("ptx", "proof") and rank == 0:
         gpu.prof_reset()
         one_unit(0, 10_000_000)
         gpu.synchronize()
@@ -375,7 +436,7 @@ def main():
 
     name, tot_ms, cnt, alg_bytes = dom
     roofline = None
-    if cnt > 0 and tot_ms > 0:
+    if args.full and cnt > 0 and tot_ms > 0:
         avg_s = (tot_ms / cnt) / 1e3
         achieved = alg_bytes / avg_s / 1e9
         traffic = os.environ.get("TG_TRAFFIC_BYTES_PER_LAUNCH")
@@ -404,9 +465,9 @@ def main():
             except Exception:
                 pass
 
-    # ---- CPU baseline (oracle "port", rank 0, N=1 only) ----
+    # ---- CPU baseline (oracle "port", rank 0, N=1 only; --full leg) ----
     cpu_baseline = None
-    if rank == 0 and world <= 1 and not os.environ.get("TG_SKIP_CPU_BASELINE"):
+    if args.full and rank == 0 and world <= 1 and not os.environ.get("TG_SKIP_CPU_BASELINE"):
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import oracle_ct as oc
 

@@ -1,6 +1,7 @@
 """Driver-contract checks on the committed bench lines (profiles/*.json):
 catches accidental drift in bench.py's output schema without needing a
-GPU (the lines were produced by the real bench on MI355X boxes)."""
+GPU (the lines were produced by the real bench on MI355X boxes; their
+roofline and cpu_baseline fields are what `bench.py --full` fills in)."""
 import json
 import os
 
@@ -52,6 +53,7 @@ def test_bench_script_defaults_parse():
 
     src = open(os.path.join(REPO, "bench.py")).read()
     ast.parse(src)
-    for flag in ["--gpus", "--steps", "--warmup", "--workload", "--streams"]:
+    for flag in ["--gpus", "--steps", "--warmup", "--workload", "--streams",
+                 "--full", "--dump-outputs"]:
         assert flag in src
     assert '"metric"' in src and '"vs_baseline"' in src
