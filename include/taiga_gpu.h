@@ -63,7 +63,13 @@ const char* tg_error_string(const tg_ctx* ctx);
 /* ---- SRS (replaces Params::read + commit bases residency;
  *      constant.rs:128-139) ----
  * Parses the params_15 byte format, uploads and decompresses both base sets
- * into HBM (they stay resident; g_lagrange never changes between proofs). */
+ * into HBM (they stay resident; g_lagrange never changes between proofs).
+ * Returns TG_ERR_ENCODING for an invalid point encoding, and also for a
+ * degenerate SRS: g or g_lagrange holding the identity or two points with the
+ * same x coordinate (a repeat, or a point and its negation), or w or u being
+ * the identity. MSMs over the SRS sets use an accumulation kernel without
+ * identity / equal-x handling, and such an SRS commits to nothing. After a
+ * rejected load the context holds no SRS (tg_srs_k gives TG_ERR_NOSRS). */
 int tg_load_srs(tg_ctx* ctx, const uint8_t* params_bytes, size_t len);
 int tg_srs_k(const tg_ctx* ctx); /* k, or TG_ERR_NOSRS */
 
@@ -73,7 +79,10 @@ int tg_srs_k(const tg_ctx* ctx); /* k, or TG_ERR_NOSRS */
  * scalars: n x 32B canonical (vesta::Scalar = pallas::Base = Fp).
  * out_xy: 64B canonical affine result. */
 int tg_bases_upload(tg_ctx* ctx, const uint8_t* points_xy, size_t n);
-/* synthetic distinct bases generated on-device ([seed+i+1]G) for benches */
+/* synthetic distinct bases generated on-device for benches: base i is
+ * [k_i]G with k_i a 256-bit scalar derived from (seed, i) by splitmix64 —
+ * random multiples, like SRS points, byte-identical to the oracle's
+ * orc_gen_bases. MSMs over them take the fast accumulation path. */
 int tg_gen_bases(tg_ctx* ctx, size_t n, uint64_t seed);
 /* read back the current base set as n x 64B canonical affine (test/debug:
  * lets parity tests diff device-generated bases against the oracle's) */

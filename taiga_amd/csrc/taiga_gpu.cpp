@@ -9,6 +9,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -334,6 +336,24 @@ int tg_prof_get(tg_ctx* ctx, const char* name, double* total_ms, long* count) {
 
 // ---------- SRS ----------
 
+// true when a set of compressed points holds the identity (all-zero x) or two
+// points with the same x (a repeat, or a point and its negation). MSMs over
+// the SRS sets run the branch-free accumulation (jac_add_aff_fast), whose
+// precondition is exactly that neither occurs. One sort of the sign-masked
+// encodings, once per load.
+static bool srs_set_degenerate(const uint8_t* set, u64 cnt, bool check_dups) {
+  std::vector<std::array<uint8_t, 32>> enc(cnt);
+  const std::array<uint8_t, 32> zero{};
+  for (u64 i = 0; i < cnt; i++) {
+    memcpy(enc[i].data(), set + 32 * i, 32);
+    enc[i][31] &= 0x7F;
+    if (enc[i] == zero) return true;
+  }
+  if (!check_dups) return false;
+  std::sort(enc.begin(), enc.end());
+  return std::adjacent_find(enc.begin(), enc.end()) != enc.end();
+}
+
 int tg_load_srs(tg_ctx* ctx, const uint8_t* bytes, size_t len) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
@@ -343,6 +363,12 @@ int tg_load_srs(tg_ctx* ctx, const uint8_t* bytes, size_t len) {
   if (k > 28) return TG_ERR_BADARG;
   u64 n = 1ULL << k;
   if (len != 4 + 2 * n * 32 + 64) return TG_ERR_BADARG;
+  // from here on the old SRS is replaced: a rejected load leaves none
+  c->k = -1;
+  if (srs_set_degenerate(bytes + 4, n, true) ||
+      srs_set_degenerate(bytes + 4 + 32 * n, n, true) ||
+      srs_set_degenerate(bytes + 4 + 64 * n, 2, false))
+    return TG_ERR_ENCODING;
   hipError_t e;
   if (c->d_g) { hipFree(c->d_g); c->d_g = nullptr; }
   if (c->d_gl) { hipFree(c->d_gl); c->d_gl = nullptr; }

@@ -1,0 +1,353 @@
+"""CPU-side test of the product's own 255-bit arithmetic.
+
+pasta_device.hpp is __host__ __device__ and the host shim uses it for the
+final MSM combine, so the same source the kernels run can be exercised here
+without a GPU: tests/host/arith_probe.cpp is compiled with hipcc, fed
+operations on stdin and compared with Python integers and oracle/pypasta.py.
+Everything is exact. Skips only when hipcc is absent."""
+import os
+import random
+import shutil
+import subprocess
+
+import pytest
+
+import pypasta as pp
+from conftest import REPO
+from kernel_shapes import (MSM_BIG_BUCKET, MSM_BIG_LANES, MSM_C_MAX, MSM_NBUCK_MAX,
+                           MSM_NWIN_MAX, MSM_SEG, MSM_TABLE, edge_values,
+                           expected_msm_cfg, msm_cfg_sample_sizes, signed_digits)
+
+HIPCC = shutil.which("hipcc") or (
+    "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
+
+pytestmark = pytest.mark.skipif(HIPCC is None, reason="hipcc not installed")
+
+MODS = {"p": pp.P, "q": pp.Q}
+R = 1 << 256
+
+
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    out = tmp_path_factory.mktemp("arith_probe") / "arith_probe"
+    subprocess.run(
+        [HIPCC, "-O2", "-std=c++17", "--offload-arch=gfx950",
+         "-I", os.path.join(REPO, "taiga_amd", "csrc"),
+         os.path.join(REPO, "tests", "host", "arith_probe.cpp"), "-o", str(out)],
+        check=True)
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("TG_MSM_SMALL_C", "TG_MSM_SMALL_SEG")}
+
+    def run(lines):
+        r = subprocess.run([str(out)], input="\n".join(lines) + "\n", env=env,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (r.returncode, r.stdout[-200:], r.stderr[-200:])
+        got = r.stdout.split("\n")[:-1]
+        assert len(got) == len(lines)
+        return got
+
+    return run
+
+
+def h(v):
+    return f"{v:064x}"
+
+
+def check(probe, cases):
+    """cases: (line, expected output line, label)"""
+    got = probe([c[0] for c in cases])
+    bad = [(c[2], g, c[1]) for c, g in zip(cases, got) if g != c[1]]
+    assert not bad, f"{len(bad)} of {len(cases)} wrong; first: {bad[:3]}"
+
+
+def pairs_for(mod, seed):
+    ev = edge_values(mod)
+    pairs = [(a, b) for a in ev for b in ev]
+    # a + b == p and a == b, beyond the ones the edge set already forms
+    pairs += [(a, mod - a) for a in ev if a]
+    rng = random.Random(seed)
+    for _ in range(2000):
+        pairs.append((rng.randrange(mod), rng.randrange(mod)))
+    for _ in range(50):
+        a = rng.randrange(1, mod)
+        pairs += [(a, mod - a), (a, a)]
+    return ev, pairs
+
+
+# ---------------- field ----------------
+
+@pytest.mark.parametrize("f", ["p", "q"])
+def test_field_binary_ops(probe, f):
+    mod = MODS[f]
+    rinv = pow(R, -1, mod)
+    ev, pairs = pairs_for(mod, 11 if f == "p" else 12)
+    assert any(a + b == mod for a, b in pairs) and any(a == b for a, b in pairs)
+    cases = []
+    for a, b in pairs:
+        cases.append((f"add {f} {h(a)} {h(b)}", h((a + b) % mod), ("add", a, b)))
+        cases.append((f"sub {f} {h(a)} {h(b)}", h((a - b) % mod), ("sub", a, b)))
+        cases.append((f"mul {f} {h(a)} {h(b)}", h(a * b * rinv % mod), ("mul", a, b)))
+    check(probe, cases)
+
+
+@pytest.mark.parametrize("f", ["p", "q"])
+def test_field_unary_ops(probe, f):
+    mod = MODS[f]
+    rinv = pow(R, -1, mod)
+    rng = random.Random(21 if f == "p" else 22)
+    vals = edge_values(mod) + [rng.randrange(mod) for _ in range(2000)]
+    cases = []
+    for a in vals:
+        cases.append((f"neg {f} {h(a)}", h(-a % mod), ("neg", a)))
+        cases.append((f"sqr {f} {h(a)}", h(a * a * rinv % mod), ("sqr", a)))
+        cases.append((f"tomont {f} {h(a)}", h(a * R % mod), ("tomont", a)))
+        cases.append((f"frommont {f} {h(a)}", h(a * rinv % mod), ("frommont", a)))
+        cases.append((f"rt {f} {h(a)}", h(a), ("rt", a)))
+        cases.append((f"isodd {f} {h(a)}", str(a * rinv % mod & 1), ("isodd", a)))
+    check(probe, cases)
+
+
+@pytest.mark.parametrize("f", ["p", "q"])
+def test_field_inv_pow(probe, f):
+    mod = MODS[f]
+    rng = random.Random(31 if f == "p" else 32)
+    ev = edge_values(mod)
+    vals = ev + [rng.randrange(mod) for _ in range(200)]
+    cases = []
+    for a in vals:
+        # Fermat a^(p-2): inv(0) comes out as 0, and is pinned to that
+        exp = pow(a, mod - 2, mod)
+        assert exp == (pow(a, -1, mod) if a else 0)
+        cases.append((f"inv {f} {h(a)}", h(exp), ("inv", a)))
+    exps = [0, 1, 2, 3, 5, 2**16, 2**31 - 1, 2**32 - 1, 2**32, 2**63, 2**64 - 1]
+    for a in ev + vals[-20:]:
+        for e in exps + [rng.getrandbits(64)]:
+            cases.append((f"pow {f} {h(a)} {e}", h(pow(a, e, mod)), ("pow", a, e)))
+    check(probe, cases)
+
+
+@pytest.mark.parametrize("f", ["p", "q"])
+def test_field_sqrt(probe, f):
+    mod = MODS[f]
+    rng = random.Random(41 if f == "p" else 42)
+    # pinned: 0 -> (true, 0); 4 is a square; 5 generates Fp* and Fq*, so it
+    # is a non-residue in both
+    assert pow(5, (mod - 1) // 2, mod) == mod - 1
+    vals = [0, 4, 5] + edge_values(mod) + [rng.randrange(mod) for _ in range(300)]
+    vals += [v * v % mod for v in vals[:40]]
+    got = probe([f"sqrt {f} {h(a)}" for a in vals])
+    n_sq = n_non = 0
+    for a, g in zip(vals, got):
+        is_sq = a == 0 or pow(a, (mod - 1) // 2, mod) == 1
+        t = g.split()
+        assert t[0] == ("1" if is_sq else "0"), (a, g)
+        if is_sq:
+            r = int(t[1], 16)
+            assert r < mod and r * r % mod == a, (a, g)
+            ref = pp.sqrt_mod(a, mod)
+            assert r in (ref, mod - ref)
+            n_sq += 1
+        else:
+            assert len(t) == 1
+            n_non += 1
+    assert got[0] == "1 " + h(0)
+    assert got[1].split()[1] in (h(2), h(mod - 2))
+    assert got[2] == "0"
+    assert n_sq > 100 and n_non > 100
+
+
+# ---------------- curve (Vesta: coordinates in Fq, group order P) ----------
+
+G = pp.Point.generator(pp.Q)
+ID = pp.Point.identity(pp.Q)
+
+
+def jac(pt, lam=1):
+    """Jacobian form of pt scaled by lam (Z = lam); identity -> Z = 0."""
+    if pt.inf:
+        return (lam % pp.Q, lam * lam % pp.Q, 0)  # X, Y arbitrary when Z == 0
+    return (pt.x * lam * lam % pp.Q, pt.y * pow(lam, 3, pp.Q) % pp.Q, lam % pp.Q)
+
+
+def jstr(j):
+    return " ".join(h(v) for v in j)
+
+
+def astr(pt):
+    return f"{h(0)} {h(0)}" if pt.inf else f"{h(pt.x)} {h(pt.y)}"
+
+
+def from_jac_line(line):
+    X, Y, Z = (int(v, 16) for v in line.split())
+    assert X < pp.Q and Y < pp.Q and Z < pp.Q
+    if Z == 0:
+        return ID
+    zi = pow(Z, -1, pp.Q)
+    return pp.Point(X * zi * zi, Y * pow(zi, 3, pp.Q), pp.Q)
+
+
+def from_aff_line(line):
+    x, y = (int(v, 16) for v in line.split())
+    assert x < pp.Q and y < pp.Q
+    return ID if x == 0 and y == 0 else pp.Point(x, y, pp.Q)
+
+
+def operand_points(rng):
+    Pt = G.mul(rng.randrange(1, pp.P))
+    return Pt, [Pt, -Pt, Pt.double(), ID, G, G.mul(rng.randrange(1, pp.P))]
+
+
+def test_curve_full_ops(probe):
+    rng = random.Random(51)
+    lines, exp = [], []
+    for _ in range(6):
+        Pt, pts = operand_points(rng)
+        forms = []
+        for pt in pts:
+            forms += [(pt, jac(pt, 1)), (pt, jac(pt, rng.randrange(2, pp.Q))),
+                      (pt, jac(pt, rng.randrange(2, pp.Q)))]
+        forms.append((ID, (0, 0, 0)))
+        for pt, j in forms:
+            lines.append("jdbl " + jstr(j)); exp.append(("j", pt.double()))
+            lines.append("jneg " + jstr(j)); exp.append(("j", -pt))
+            lines.append("j2a " + jstr(j)); exp.append(("a", pt))
+        # every ordered pairing: P+P, P+(-P), id+P, P+id, id+id and equal
+        # points under different Z are all in here
+        for pa, ja in forms:
+            for pb, jb in forms:
+                lines.append(f"jadd {jstr(ja)} {jstr(jb)}"); exp.append(("j", pa + pb))
+        for pt in pts:
+            lines.append("aneg " + astr(pt)); exp.append(("a", -pt))
+            if not pt.inf:
+                lines.append("anegf " + astr(pt)); exp.append(("a", -pt))
+    kinds = {l.split()[0] for l in lines}
+    assert kinds == {"jdbl", "jneg", "j2a", "jadd", "aneg", "anegf"}
+    got = probe(lines)
+    for line, (kind, want), g in zip(lines, exp, got):
+        have = from_jac_line(g) if kind == "j" else from_aff_line(g)
+        assert have == want, (line.split()[0], line, g)
+        if kind == "a" and want.inf:
+            assert g == f"{h(0)} {h(0)}"
+
+
+def test_curve_mixed_add_exceptional(probe):
+    rng = random.Random(52)
+    lines, exp = [], []
+    for _ in range(6):
+        Pt, pts = operand_points(rng)
+        for pa in pts:
+            for lam in (1, rng.randrange(2, pp.Q), rng.randrange(2, pp.Q)):
+                ja = jac(pa, lam)
+                for pb in pts:
+                    for op in ("jadda", "jaddi"):
+                        lines.append(f"{op} {jstr(ja)} {astr(pb)}")
+                        exp.append(pa + pb)
+                    # the branch-free add only where its precondition holds
+                    if not pa.inf and not pb.inf and pa.x != pb.x:
+                        lines.append(f"jaddf {jstr(ja)} {astr(pb)}")
+                        exp.append(pa + pb)
+    got = probe(lines)
+    seen = set()
+    for line, want, g in zip(lines, exp, got):
+        assert from_jac_line(g) == want, (line.split()[0], line, g)
+        seen.add((line.split()[0], want.inf))
+    # both the annihilating and the ordinary outcome occurred for the safe adds
+    assert {("jadda", True), ("jadda", False), ("jaddi", True), ("jaddi", False),
+            ("jaddf", False)} <= seen
+
+
+def test_curve_fast_add_equals_safe_add(probe):
+    rng = random.Random(53)
+    lines = []
+    pts = []
+    for _ in range(200):
+        a, b = G.mul(rng.randrange(1, pp.P)), G.mul(rng.randrange(1, pp.P))
+        assert a.x != b.x
+        ja = jac(a, rng.choice((1, rng.randrange(2, pp.Q))))
+        lines.append(f"jaddf {jstr(ja)} {astr(b)}")
+        lines.append(f"jaddi {jstr(ja)} {astr(b)}")
+        pts.append(a + b)
+    got = probe(lines)
+    for i, want in enumerate(pts):
+        # same formulas, so the Jacobian triples agree limb for limb
+        assert got[2 * i] == got[2 * i + 1]
+        assert from_jac_line(got[2 * i]) == want
+
+
+# ---------------- msm_cfg and msm_host_combine ----------------
+
+def test_msm_constants_pinned(probe):
+    got = [int(v) for v in probe(["consts"])[0].split()]
+    assert got == [MSM_C_MAX, MSM_NWIN_MAX, MSM_NBUCK_MAX, MSM_SEG, MSM_BIG_BUCKET,
+                   MSM_BIG_LANES]
+
+
+def test_msm_cfg_table_and_invariants(probe):
+    ns = msm_cfg_sample_sizes()
+    got = probe([f"cfg {n}" for n in ns])
+    seen_c = set()
+    for n, g in zip(ns, got):
+        c, nwin, nbuck, nseg, seg = (int(v) for v in g.split())
+        assert (c, nwin, nbuck, nseg, seg) == tuple(expected_msm_cfg(n)), n
+        seen_c.add(c)
+        assert nwin * c >= 255
+        assert nwin <= 32
+        assert nbuck == 1 << (c - 1)
+        assert nseg * seg == nbuck
+        assert nwin * nbuck <= MSM_NWIN_MAX * MSM_NBUCK_MAX
+        assert nwin * nseg <= MSM_NWIN_MAX * 2 * MSM_NBUCK_MAX // MSM_SEG
+        # the largest canonical scalar must not carry out of the top window,
+        # and its top digit must still be a valid bucket
+        for s in (pp.P - 1, pp.P - 2, 2**254, 2**254 - 1):
+            digs, carry = signed_digits(s, c, nwin)
+            assert carry == 0
+            top_raw = s >> ((nwin - 1) * c)
+            assert top_raw + 1 <= 1 << (c - 1)
+            assert all(-(1 << (c - 1)) < d <= 1 << (c - 1) for d in digs)
+            assert sum(d << (c * w) for w, d in enumerate(digs)) == s
+    assert seen_c == set(MSM_TABLE)
+    # the table itself, as the launcher documents it
+    for lo, hi, c in ((1, 2**11 - 1, 8), (2**11, 2**12 - 1, 9), (2**12, 2**13 - 1, 10),
+                      (2**13, 2**14 - 1, 11), (2**14, 2**15 - 1, 12),
+                      (2**15, 2**18 - 1, 13), (2**18, 2**20 + 1, 16)):
+        assert expected_msm_cfg(lo).c == c and expected_msm_cfg(hi).c == c
+
+
+def test_msm_host_combine(probe):
+    rng = random.Random(61)
+    small = {d: G.mul(d) for d in (1, 2, 3)}
+
+    def mulG(d):
+        if d == 0:
+            return ID
+        pt = small.get(abs(d)) or G.mul(abs(d))
+        return -pt if d < 0 else pt
+
+    lines, exp = [], []
+    for c, cfg in sorted(MSM_TABLE.items()):
+        nwin = cfg.nwin
+        full = 1 << c
+        cases = [
+            [rng.randrange(full) for _ in range(nwin)],
+            [rng.randrange(-full // 2, full // 2 + 1) for _ in range(nwin)],
+            [0] * nwin,
+            [1] * nwin,
+            [0] * (nwin - 1) + [1],
+            [1] + [0] * (nwin - 1),
+            # acc == wsum when it is added (P+P) ...
+            [rng.randrange(full) for _ in range(nwin - 2)] + [full, 1],
+            # ... and acc == -wsum (P+(-P)), then identity operands below it
+            [0] * (nwin - 2) + [-full, 1],
+            [rng.randrange(full) for _ in range(nwin - 3)] + [0, -full, 1],
+        ]
+        for digs in cases:
+            ws = []
+            for d in digs:
+                lam = rng.choice((1, rng.randrange(2, pp.Q)))
+                ws.append(jstr(jac(mulG(d), lam)))
+            lines.append(f"comb {c} {nwin} " + " ".join(ws))
+            total = sum(d << (c * w) for w, d in enumerate(digs)) % pp.P
+            exp.append(G.mul(total))
+    got = probe(lines)
+    for line, want, g in zip(lines, exp, got):
+        assert from_aff_line(g) == want, line[:12]
