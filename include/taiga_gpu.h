@@ -197,8 +197,8 @@ int tg_witness_hash(tg_ctx* ctx, const uint8_t inst_seed[32],
  * "Taiga_RedPallasH" wide-reduced to the Pallas scalar field; signature =
  * 32B compressed R ‖ 32B LE scalar S; sign nonce = H*(T ‖ vk ‖ msg) with
  * T = 80 ChaCha20-DRBG bytes from rng_seed. Ctx-free host calls. The
- * basepoint is the Pallas generator pending the sinsemilla group-hash
- * chain for RESOURCE_COMMIT_DOMAIN.R() (constant.rs:160).
+ * basepoint is the reference's RESOURCE_COMMIT_DOMAIN.R() (constant.rs:160),
+ * pinned against its window tables (tests/test_fixed_base_tables.py).
  * Scalars are 32B LE canonical mod the Pallas group order. */
 int tg_binding_vk(const uint8_t sk[32], uint8_t vk_out[32]);
 int tg_delta_commit(const uint8_t r[32], uint8_t cv_out[32]);

@@ -7,9 +7,8 @@
  * BLAKE2b-512 "Taiga_RedPallasH" wide-reduced into the Pallas scalar
  * field) and Transaction::digest (transaction.rs:116-158 — BLAKE2b-256
  * "TxBindingSigHash" over nullifiers ‖ cms ‖ delta commitments ‖
- * anchors). Basepoint: Pallas generator for round 1 (the reference's
- * sinsemilla-derived R generator, constant.rs:160, lands with the
- * group-hash chain — DESIGN.md §6).
+ * anchors). Basepoint: the reference's sinsemilla-derived
+ * RESOURCE_COMMIT_DOMAIN.R() (constant.rs:160), pinned in pallas_gen below.
  */
 #include <stdint.h>
 #include <string.h>

@@ -13,13 +13,9 @@
 //   - sign nonce r = H*(T ‖ vk_bytes ‖ msg), T = 80 bytes of caller
 //     randomness (here: a ChaCha20 DRBG stream from a 32-byte seed, the
 //     same deterministic-randomness convention as the prover)
-// Basepoint: the reference uses the sinsemilla-derived
-// RESOURCE_COMMIT_DOMAIN.R() (constant.rs:160); deriving that point needs
-// the Pallas group-hash (simplified-SWU + isogeny) chain, which is the
-// round-2 item alongside poseidon_to_curve. Until then the basepoint is
-// the Pallas generator, pinned in DESIGN.md §6 as an assumed slot — the
-// algorithm, digest layout and delta-aggregation below are basepoint-
-// independent.
+// Basepoint: the reference's sinsemilla-derived
+// RESOURCE_COMMIT_DOMAIN.R() (constant.rs:160), pinned in
+// pallas_basepoint() below.
 //
 // The binding vk aggregates a bundle's delta commitments
 // (transaction.rs:99-114): vk = Σ cv_i, sk = Σ r_i, which closes for
@@ -92,11 +88,7 @@ inline bool pallas_decompress(PallasJac& out, const uint8_t in[32]) {
     out = jac_identity<FpCfg>();
     return true;
   }
-  for (int limb = 3;; limb--) {
-    if (x.l[limb] > FpCfg::MOD[limb]) return false;
-    if (x.l[limb] < FpCfg::MOD[limb]) break;
-    if (limb == 0) return false;
-  }
+  if (!fd_is_canonical(x)) return false;
   Fp xm = fd_to_mont(x);
   Fp five{{5, 0, 0, 0}};
   Fp rhs = fd_add(fd_mul(fd_sqr(xm), xm), fd_to_mont(five));
@@ -125,11 +117,7 @@ inline Fq bs_hstar(const uint8_t* a, size_t alen, const uint8_t* b, size_t blen,
 inline bool bs_scalar_from_bytes(Fq& out, const uint8_t in[32]) {
   Fq v;
   memcpy(v.l, in, 32);
-  for (int limb = 3;; limb--) {
-    if (v.l[limb] > FqCfg::MOD[limb]) return false;
-    if (v.l[limb] < FqCfg::MOD[limb]) break;
-    if (limb == 0) return false;
-  }
+  if (!fd_is_canonical(v)) return false;
   out = fd_to_mont(v);
   return true;
 }

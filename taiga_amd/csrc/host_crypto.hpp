@@ -298,13 +298,6 @@ struct Transcript {
   }
 
   // ---- read mode (verifier) ----
-  static bool fq_canonical(const Fq& v) {
-    for (int limb = 3; limb >= 0; limb--) {
-      if (v.l[limb] > FqCfg::MOD[limb]) return false;
-      if (v.l[limb] < FqCfg::MOD[limb]) return true;
-    }
-    return false;
-  }
 
   // 32-byte compressed -> Mont affine (host Tonelli-Shanks); rejects
   // identity and invalid encodings (transcript points are never identity)
@@ -315,7 +308,7 @@ struct Transcript {
     l[3] &= 0x7FFFFFFFFFFFFFFFULL;
     if ((l[0] | l[1] | l[2] | l[3]) == 0) return false;
     Fq x{{l[0], l[1], l[2], l[3]}};
-    if (!fq_canonical(x)) return false;
+    if (!fd_is_canonical(x)) return false;
     Fq xm = fd_to_mont(x);
     Fq five{{5, 0, 0, 0}};
     Fq rhs = fd_add(fd_mul(fd_sqr(xm), xm), fd_to_mont(five));
@@ -339,11 +332,7 @@ struct Transcript {
     if (rpos + 32 > rlen) return false;
     Fp v;
     memcpy(v.l, rbuf + rpos, 32);
-    for (int limb = 3;; limb--) {
-      if (v.l[limb] > FpCfg::MOD[limb]) return false;
-      if (v.l[limb] < FpCfg::MOD[limb]) break;
-      if (limb == 0) return false;
-    }
+    if (!fd_is_canonical(v)) return false;
     rpos += 32;
     s = fd_to_mont(v);
     common_scalar(s);

@@ -49,23 +49,12 @@ inline MsmCfg msm_cfg(long n) {
   // floored at 8 to keep nwin <= 32 for the d_dig/d_wsums allocs): the prover's
   // n=2^15 commits take c=13, the IPA's geometrically shrinking rounds
   // smaller windows still. Reduce segments sized so nseg <= 1024 per
-  // window. TG_MSM_SMALL_C/SEG override for A/B probes only (results are
-  // windowing-independent).
-  static int sc_env = [] {
-    const char* e = getenv("TG_MSM_SMALL_C");
-    int v = e ? atoi(e) : 0;
-    return (v >= 8 && v <= 16) ? v : 0; /* nwin <= 32 (d_dig/d_wsums allocs) */
-  }();
-  static int sseg_env = [] {
-    const char* e = getenv("TG_MSM_SMALL_SEG");
-    int v = e ? atoi(e) : 0;
-    return (v >= 1 && v <= 64) ? v : 0;
-  }();
+  // window.
   int lg = 0;
   while ((1L << (lg + 1)) <= n) lg++;
-  int sc = sc_env ? sc_env : (lg - 2 < 8 ? 8 : (lg - 2 > 13 ? 13 : lg - 2));
+  int sc = lg - 2 < 8 ? 8 : (lg - 2 > 13 ? 13 : lg - 2);
   int nbuck = 1 << (sc - 1);
-  int sseg = sseg_env ? sseg_env : (nbuck / 1024 > 0 ? nbuck / 1024 : 1);
+  int sseg = nbuck / 1024 > 0 ? nbuck / 1024 : 1;
   return MsmCfg{sc, (255 + sc - 1) / sc, nbuck, nbuck / sseg, sseg};
 }
 
@@ -537,20 +526,12 @@ static inline int msm_grid(u64 work, int block = 256) {
 
 // counting-sort bucket ids by length into w.d_order (see MSM_LEN_BINS note);
 // call between k_scatter (start/end final) and k_bucket_acc. Returns the
-// order array to hand to k_bucket_acc (null = sort disabled via
-// TG_MSM_LEN_SORT=0, A/B only). Measured on MI355X: 1.44x on k_bucket_acc
-// at the prover's c=13 (Poisson(8) buckets, wave runs at max-of-64 ~ 19
-// without it) and 1.15x at c=16/n=2^20 — but ONLY with the LDS-aggregated
-// histogram/scatter below; the first cut's per-item global atomics on 66
-// bins serialized the whole chip across all proving streams.
-inline const uint32_t* msm_len_sort(MsmWork& w, const MsmCfg& cfg, u64 m,
-                                    hipStream_t stream) {
-  static int force = [] {
-    const char* e = getenv("TG_MSM_LEN_SORT");
-    return e ? (atoi(e) ? 1 : 0) : -1;
-  }();
-  if (force == 0) return nullptr;
-  (void)cfg;
+// order array to hand to k_bucket_acc. Measured on MI355X: 1.44x on
+// k_bucket_acc at the prover's c=13 (Poisson(8) buckets, wave runs at
+// max-of-64 ~ 19 without it) and 1.15x at c=16/n=2^20 — but ONLY with the
+// LDS-aggregated histogram/scatter below; the first cut's per-item global
+// atomics on 66 bins serialized the whole chip across all proving streams.
+inline const uint32_t* msm_len_sort(MsmWork& w, u64 m, hipStream_t stream) {
   hipMemsetAsync(w.d_lhist, 0, MSM_LEN_BINS * 4, stream);
   hipLaunchKernelGGL(k_len_hist, dim3(msm_grid(m)), dim3(256), 0, stream, w.d_hist,
                      w.d_end, m, w.d_lhist);
@@ -560,16 +541,102 @@ inline const uint32_t* msm_len_sort(MsmWork& w, const MsmCfg& cfg, u64 m,
   return w.d_order;
 }
 
-// host-side final combine: acc = sum_w 2^(16w) * wsum[w]  (Horner, ~240
+// bucket accumulation, both phases. SAFE handles identity/duplicate bases
+// (caller-uploaded sets); the branch-free variant needs distinct
+// non-identity bases (SRS sets, gen_bases output).
+template <bool SAFE>
+inline void msm_acc_launch(MsmWork& w, u64 m, const VestaAff* bases, const uint32_t* ord,
+                           hipStream_t stream) {
+  hipLaunchKernelGGL(k_bucket_acc<SAFE>, dim3(msm_grid(m)), dim3(256), 0, stream,
+                     w.d_hist, w.d_end, w.d_sorted, bases, w.d_buckets, m, w.d_big,
+                     w.d_big + m, ord);
+  hipLaunchKernelGGL(k_bucket_acc_big<SAFE>, dim3(1024), dim3(MSM_BIG_LANES), 0, stream,
+                     w.d_hist, w.d_end, w.d_sorted, bases, w.d_buckets, w.d_big,
+                     w.d_big + m);
+}
+
+// prof indices of msm_run: the six stages in P_MSM_* order, then the two
+// accumulation kernels alone (inside MSM_P_ACC, which also covers the
+// length sort), then the whole chain up to the window sums.
+enum {
+  MSM_P_DIGITS = 0, MSM_P_SCAN, MSM_P_SCATTER, MSM_P_ACC, MSM_P_REDUCE, MSM_P_WSUM,
+  MSM_P_ACC_KERNELS, MSM_P_CHAIN,
+};
+
+// the unprofiled ProfFn
+inline int msm_noprof(int) { return 0; }
+
+// B same-size MSMs (nn points each, n = nn * B canonical device scalars)
+// over ONE device base array: enqueues the whole kernel chain on stream and
+// the copy of the cfg.nwin * B Jacobian window sums to host wsums (valid
+// after the caller synchronizes the stream; combine each MSM's nwin sums
+// with msm_host_combine*). w must be msm_work_alloc'ed for (n, B).
+// ProfFn: callable int->RAII scope, as in ntt_run (msm_noprof for none).
+template <class ProfFn>
+inline void msm_run(MsmWork& w, const ScalarRepr* d_scalars, u64 n, u64 nn, u64 B,
+                    const VestaAff* bases, bool safe, hipStream_t stream,
+                    VestaJac* wsums, ProfFn&& prof) {
+  MsmCfg cfg = msm_cfg((long)nn);
+  u64 m = (u64)cfg.nwin * cfg.nbuck * B;
+  {
+    [[maybe_unused]] auto chain = prof(MSM_P_CHAIN);
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_DIGITS);
+      hipMemsetAsync(w.d_hist, 0, m * 4, stream);
+      hipLaunchKernelGGL(k_digits, dim3(msm_grid(n)), dim3(256), 0, stream, d_scalars, n,
+                         nn, cfg, w.d_dig, w.d_hist);
+    }
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_SCAN);
+      msm_scan(w.d_hist, w.d_off, w.d_bsum, m, stream);
+      hipMemcpyAsync(w.d_hist, w.d_off, m * 4, hipMemcpyDeviceToDevice, stream);
+    }
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_SCATTER);
+      hipLaunchKernelGGL(k_scatter, dim3(msm_grid(n)), dim3(256), 0, stream, w.d_dig, n,
+                         nn, cfg, w.d_off, w.d_sorted);
+      hipMemcpyAsync(w.d_end, w.d_off, m * 4, hipMemcpyDeviceToDevice, stream);
+    }
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_ACC);
+      hipMemsetAsync(w.d_big + m, 0, 4, stream);
+      const uint32_t* ord = msm_len_sort(w, m, stream);
+      [[maybe_unused]] auto pk = prof(MSM_P_ACC_KERNELS);
+      if (safe)
+        msm_acc_launch<true>(w, m, bases, ord, stream);
+      else
+        msm_acc_launch<false>(w, m, bases, ord, stream);
+    }
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_REDUCE);
+      hipLaunchKernelGGL(k_bucket_reduce, dim3(msm_grid((u64)cfg.nwin * B * cfg.nseg)),
+                         dim3(256), 0, stream, w.d_buckets, w.d_partials,
+                         (u64)cfg.nwin * B, cfg);
+    }
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_WSUM);
+      hipLaunchKernelGGL(k_wsum, dim3(cfg.nwin * B), dim3(256), 0, stream, w.d_partials,
+                         w.d_wsums, cfg);
+    }
+  }
+  hipMemcpyAsync(wsums, w.d_wsums, sizeof(VestaJac) * cfg.nwin * B, hipMemcpyDeviceToHost,
+                 stream);
+}
+
+// host-side final combine: acc = sum_w 2^(c*w) * wsum[w]  (Horner, ~240
 // doublings of O(1) work — the same TG_HD primitives as the kernels)
-inline VestaAff msm_host_combine(const VestaJac* wsums, const MsmCfg& cfg) {
+inline VestaJac msm_host_combine_jac(const VestaJac* wsums, const MsmCfg& cfg) {
   VestaJac acc = jac_identity<FqCfg>();
   for (int w = cfg.nwin - 1; w >= 0; w--) {
     if (w != cfg.nwin - 1)
       for (int b = 0; b < cfg.c; b++) acc = jac_dbl(acc);
     acc = jac_add(acc, wsums[w]);
   }
-  return jac_to_aff(acc);
+  return acc;
+}
+
+inline VestaAff msm_host_combine(const VestaJac* wsums, const MsmCfg& cfg) {
+  return jac_to_aff(msm_host_combine_jac(wsums, cfg));
 }
 
 }  // namespace taiga

@@ -35,28 +35,13 @@ __device__ __forceinline__ u64 bitrev(u64 x, int k) {
   return r;
 }
 
-// out[i] = to_mont(in[bitrev(i)]); sets *err if any input repr >= MOD.
+// out[i] = in[bitrev(i)] (sizes below the fused first pass's tile)
 template <class C>
-__global__ void __launch_bounds__(256) k_bitrev_load(Fd<C>* out, const Fd<C>* in, int k, int to_mont_flag,
-                              unsigned* err) {
+__global__ void __launch_bounds__(256) k_bitrev_load(Fd<C>* out, const Fd<C>* in, int k) {
   u64 n = 1ULL << k;
   for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n;
-       i += (u64)gridDim.x * blockDim.x) {
-    Fd<C> v = in[bitrev(i, k)];
-    if (err) {
-      // canonical check: v < MOD
-      bool ge = true;  // ge stays true only if v == MOD prefix-equal path
-      bool lt = false;
-#pragma unroll
-      for (int limb = 3; limb >= 0; limb--) {
-        if (!lt && v.l[limb] > C::MOD[limb]) { atomicOr(err, 1u); break; }
-        if (v.l[limb] < C::MOD[limb]) { lt = true; }
-      }
-      if (!lt) atomicOr(err, 1u);
-      (void)ge;
-    }
-    out[i] = to_mont_flag ? fd_to_mont(v) : v;
-  }
+       i += (u64)gridDim.x * blockDim.x)
+    out[i] = in[bitrev(i, k)];
 }
 
 // one radix-2 DIT stage s (1-based): butterflies on pairs span 2^(s-1)
@@ -78,59 +63,12 @@ __global__ void __launch_bounds__(256) k_ntt_stage(Fd<C>* a, const Fd<C>* tw, in
   }
 }
 
-// fused LDS stages: processes FUSE stages [s0+1 .. s0+FUSE] in one pass.
-// Each block handles TILE = 2^FUSE_LOG consecutive butterfly-groups worth of
-// elements gathered with stride 2^s0 elements.
-// Tile size chosen so 256 threads * 2 elements/thread = 512 elements in LDS.
-template <class C, int FUSE>
-__global__ void __launch_bounds__(256) k_ntt_fused(Fd<C>* a, const Fd<C>* tw, int k, int s0) {
-  // elements per tile
-  constexpr int TILE = 1 << FUSE;           // e.g. 32.. but we use 512 = 2^9
-  __shared__ Fd<C> lds[1 << FUSE];
-  u64 n = 1ULL << k;
-  u64 span = 1ULL << s0;                    // input butterfly span entering this pass
-  // tile t handles elements idx = base + m*span for m in [0, TILE), where
-  // tiles partition each contiguous "segment" of length span*TILE.
-  u64 tiles_per_seg = span;                 // one tile per residue class r < span
-  u64 seg_len = span << FUSE;
-  u64 nseg = n / seg_len;
-  u64 ntiles = nseg * tiles_per_seg;
-  for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    u64 seg = tile / tiles_per_seg;
-    u64 r = tile % tiles_per_seg;
-    u64 base = seg * seg_len + r;
-    // load TILE strided elements
-    for (int m = threadIdx.x; m < TILE; m += blockDim.x) lds[m] = a[base + (u64)m * span];
-    __syncthreads();
-    // FUSE local stages; local stage ls corresponds to global stage s0+ls
-    for (int ls = 1; ls <= FUSE; ls++) {
-      int s = s0 + ls;
-      u64 half = 1ULL << (ls - 1);
-      int tshift = k - s;
-      for (int j = threadIdx.x; j < (TILE >> 1); j += blockDim.x) {
-        u64 grp = (u64)j >> (ls - 1);
-        u64 kk = (u64)j & (half - 1);
-        u64 i0 = (grp << ls) | kk;
-        u64 i1 = i0 + half;
-        // global butterfly index kk_global = kk*span + r, twiddle = kk_g << tshift
-        u64 kkg = (kk << s0) | r;
-        Fd<C> t = fd_mul(lds[i1], tw[kkg << tshift]);
-        Fd<C> lo = lds[i0];
-        lds[i1] = fd_sub(lo, t);
-        lds[i0] = fd_add(lo, t);
-      }
-      __syncthreads();
-    }
-    for (int m = threadIdx.x; m < TILE; m += blockDim.x) a[base + (u64)m * span] = lds[m];
-    __syncthreads();
-  }
-}
-
-// first-pass variant with the bit-reversal fused into the load: reads the
+// fused LDS first pass: stages 1..FUSE on TILE = 2^FUSE contiguous
+// elements per block, with the bit-reversal fused into the load: reads the
 // NATURAL-order input directly (a strided gather — source index =
 // bitrev_FUSE(m) << (k-FUSE) | bitrev_{k-FUSE}(tile)) and writes the
-// pass-1 result contiguously, replacing the separate k_bitrev_load sweep
-// (one full n-read + n-write saved per direction).
+// pass-1 result contiguously; a separate k_bitrev_load sweep before it
+// cost one more full n-read + n-write per direction.
 template <class C, int FUSE>
 __global__ void __launch_bounds__(256) k_ntt_fused_br(Fd<C>* out, const Fd<C>* in,
                                                       const Fd<C>* tw, int k) {
@@ -289,10 +227,13 @@ inline hipError_t ntt_plan_init(NttPlan& plan, int k, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// the ProfFn of unprofiled callers
+inline int ntt_noprof(int) { return 0; }
+
 // in-place NTT on device Montgomery-form data (d_a), size 2^k, using d_tmp
 // as the working buffer (bitrev lands there; result copied back).
 // inverse => scales by n^{-1}. ProfFn: callable int->RAII scope, bracketing
-// each launch group for the HIP-event profiler (pass a no-op for none).
+// each launch group for the HIP-event profiler (ntt_noprof for none).
 // Prof indices: 0 bitrev, 1 fused, 2 stage, 3 scale.
 template <class ProfFn>
 inline hipError_t ntt_run(Fd<FpCfg>* d_a, Fd<FpCfg>* d_tmp, const NttPlan& plan, int k,
@@ -303,13 +244,8 @@ inline hipError_t ntt_run(Fd<FpCfg>* d_a, Fd<FpCfg>* d_tmp, const NttPlan& plan,
   constexpr int FUSE = 9;  // 512-element LDS tiles (16 KiB), first pass only
   constexpr int RB = 8;    // residues per block in the strided passes (256-B gathers)
   // bitrev fused into the first pass's load when that pass exists
-  // (TG_NTT_FUSE_BR=0 restores the separate sweep for A/B)
-  static int fuse_br = [] {
-    const char* e = getenv("TG_NTT_FUSE_BR");
-    return e ? (atoi(e) ? 1 : 0) : 1;
-  }();
   int s = 1;
-  if (fuse_br && k >= FUSE) {
+  if (k >= FUSE) {
     [[maybe_unused]] auto sc = prof(1);
     u64 ntiles = n >> FUSE;
     hipLaunchKernelGGL((k_ntt_fused_br<FpCfg, FUSE>),
@@ -319,48 +255,21 @@ inline hipError_t ntt_run(Fd<FpCfg>* d_a, Fd<FpCfg>* d_tmp, const NttPlan& plan,
   } else {
     [[maybe_unused]] auto sc = prof(0);
     hipLaunchKernelGGL(k_bitrev_load<FpCfg>, dim3(ntt_grid(n)), dim3(256), 0, stream,
-                       d_tmp, d_a, k, 0, nullptr);
+                       d_tmp, d_a, k);
   }
   while (s <= k) {
     int remaining = k - s + 1;
-    if (s == 1 && remaining >= FUSE) {
-      // first pass: span 1, tiles are contiguous -> 1-D variant
-      [[maybe_unused]] auto sc = prof(1);
-      u64 ntiles = n >> FUSE;
-      hipLaunchKernelGGL((k_ntt_fused<FpCfg, FUSE>),
-                         dim3(ntiles > 2048 ? 2048 : (unsigned)ntiles), dim3(256), 0,
-                         stream, d_tmp, tw, k, s - 1);
-      s += FUSE;
-      continue;
-    }
     int f = remaining < 7 ? remaining : 7;  // RB=8 at F=7: 33 KiB LDS
     u64 span = 1ULL << (s - 1);
     if (f >= 2 && span >= RB) {
       [[maybe_unused]] auto sc = prof(1);
       u64 ntiles = n >> f;
       unsigned grid = ntiles > 2048 ? 2048 : (unsigned)ntiles;
-      // wider residue blocks for the F=7 passes (512-B / 1-KiB contiguous
-      // gathers; gfx950 allows the 66/132 KiB LDS workgroups) — MEASURED
-      // SLOWER at k=22 (RB=8: 4.20 G elem/s, 16: 3.95, 32: 3.35): the
-      // 66/132 KiB workgroups drop residency to 2/1 per CU and the lost
-      // latency hiding outweighs the wider gathers, so 256-B chunks were
-      // not the bottleneck. Kept behind TG_NTT_RB={8,16,32} as the A/B
-      // evidence; default stays 8.
-      static int rb_wide = [] {
-        const char* e = getenv("TG_NTT_RB");
-        int v = e ? atoi(e) : 8;
-        return (v == 8 || v == 16 || v == 32) ? v : 8;
-      }();
-      if (f == 7 && rb_wide == 32 && span >= 32) {
-        hipLaunchKernelGGL((k_ntt_fused2<FpCfg, 7, 32>), dim3(grid), dim3(256), 0, stream, d_tmp, tw, k, s - 1);
-        s += f;
-        continue;
-      }
-      if (f == 7 && rb_wide == 16 && span >= 16) {
-        hipLaunchKernelGGL((k_ntt_fused2<FpCfg, 7, 16>), dim3(grid), dim3(256), 0, stream, d_tmp, tw, k, s - 1);
-        s += f;
-        continue;
-      }
+      // wider residue blocks for the F=7 passes (RB=16/32: 512-B / 1-KiB
+      // contiguous gathers) MEASURED SLOWER at k=22 (RB=8: 4.20 G elem/s,
+      // 16: 3.95, 32: 3.35): the 66/132 KiB LDS workgroups drop residency
+      // to 2/1 per CU and the lost latency hiding outweighs the wider
+      // gathers, so 256-B chunks were not the bottleneck. Variants removed.
       switch (f) {
         case 7: hipLaunchKernelGGL((k_ntt_fused2<FpCfg, 7, RB>), dim3(grid), dim3(256), 0, stream, d_tmp, tw, k, s - 1); break;
         case 6: hipLaunchKernelGGL((k_ntt_fused2<FpCfg, 6, RB>), dim3(grid), dim3(256), 0, stream, d_tmp, tw, k, s - 1); break;

@@ -4,8 +4,6 @@
 
 namespace taiga {
 
-// ---------------- extra kernels ----------------
-
 // ---------------- device helpers over Ctx ----------------
 
 struct ProverDev {
@@ -61,8 +59,8 @@ static void pdev_free(ProverDev& pd) {
 static int gpu_lag_to_coeff(Ctx* c, ProverDev& pd, Fp* data, int k, const Fp& ninv) {
   long n = 1L << k;
   hipMemcpyAsync(pd.ws0, data, n * sizeof(Fp), hipMemcpyHostToDevice, c->stream);
-  auto noprof = [&](int) { return 0; };
-  if (ntt_run(pd.ws0, pd.ws1, pd.plan_n, k, true, c->stream, &ninv, noprof) != hipSuccess)
+  if (ntt_run(pd.ws0, pd.ws1, pd.plan_n, k, true, c->stream, &ninv, ntt_noprof) !=
+      hipSuccess)
     return TG_ERR_HIP;
   hipMemcpyAsync(data, pd.ws0, n * sizeof(Fp), hipMemcpyDeviceToHost, c->stream);
   return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : TG_ERR_HIP;
@@ -75,9 +73,8 @@ static int gpu_coeff_to_ext(Ctx* c, ProverDev& pd, const Fp* coeff, Fp* ext_out,
   hipMemcpyAsync(pd.ws0, coeff, n * sizeof(Fp), hipMemcpyHostToDevice, c->stream);
   hipMemsetAsync(pd.ws0 + n, 0, (ext_n - n) * sizeof(Fp), c->stream);
   coset_scale_launch(pd.ws0, (u64)ext_n, zeta, c->stream);
-  auto noprof = [&](int) { return 0; };
-  if (ntt_run(pd.ws0, pd.ws1, pd.plan_ext, ext_k, false, c->stream, nullptr, noprof) !=
-      hipSuccess)
+  if (ntt_run(pd.ws0, pd.ws1, pd.plan_ext, ext_k, false, c->stream, nullptr,
+              ntt_noprof) != hipSuccess)
     return TG_ERR_HIP;
   hipMemcpyAsync(ext_out, pd.ws0, ext_n * sizeof(Fp), hipMemcpyDeviceToHost, c->stream);
   return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : TG_ERR_HIP;
@@ -91,16 +88,16 @@ static int gpu_lag_to_coeff_ext_dev(Ctx* c, ProverDev& pd, Fp* host_lag_to_coeff
   long n = 1L << k, ext_n = 1L << ext_k;
   hipMemcpyAsync(pd.ws0, host_lag_to_coeff, n * sizeof(Fp), hipMemcpyHostToDevice,
                  c->stream);
-  auto noprof = [&](int) { return 0; };
-  if (ntt_run(pd.ws0, pd.ws1, pd.plan_n, k, true, c->stream, &ninv, noprof) != hipSuccess)
+  if (ntt_run(pd.ws0, pd.ws1, pd.plan_n, k, true, c->stream, &ninv, ntt_noprof) !=
+      hipSuccess)
     return TG_ERR_HIP;
   hipMemcpyAsync(host_lag_to_coeff, pd.ws0, n * sizeof(Fp), hipMemcpyDeviceToHost,
                  c->stream);
   hipMemcpyAsync(d_ext_dst, pd.ws0, n * sizeof(Fp), hipMemcpyDeviceToDevice, c->stream);
   hipMemsetAsync(d_ext_dst + n, 0, (ext_n - n) * sizeof(Fp), c->stream);
   coset_scale_launch(d_ext_dst, (u64)ext_n, zeta, c->stream);
-  if (ntt_run(d_ext_dst, pd.ws1, pd.plan_ext, ext_k, false, c->stream, nullptr, noprof) !=
-      hipSuccess)
+  if (ntt_run(d_ext_dst, pd.ws1, pd.plan_ext, ext_k, false, c->stream, nullptr,
+              ntt_noprof) != hipSuccess)
     return TG_ERR_HIP;
   return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : TG_ERR_HIP;
 }
@@ -112,27 +109,10 @@ static int gpu_coeff_to_ext_dev(Ctx* c, ProverDev& pd, const Fp* coeff, Fp* d_ds
   hipMemcpyAsync(d_dst, coeff, n * sizeof(Fp), hipMemcpyHostToDevice, c->stream);
   hipMemsetAsync(d_dst + n, 0, (ext_n - n) * sizeof(Fp), c->stream);
   coset_scale_launch(d_dst, (u64)ext_n, zeta, c->stream);
-  auto noprof = [&](int) { return 0; };
-  if (ntt_run(d_dst, pd.ws1, pd.plan_ext, ext_k, false, c->stream, nullptr, noprof) !=
-      hipSuccess)
+  if (ntt_run(d_dst, pd.ws1, pd.plan_ext, ext_k, false, c->stream, nullptr,
+              ntt_noprof) != hipSuccess)
     return TG_ERR_HIP;
   return 0;
-}
-
-// extended evals -> coeffs (zeta undistributed), via GPU iNTT
-// kept for host-buffer callers (the prover now keeps h on device via the
-// dH path; tests and future stages may still round-trip through host)
-[[maybe_unused]] static int gpu_ext_to_coeff(Ctx* c, ProverDev& pd, const Fp* ext_in, Fp* coeff_out,
-                            int ext_k, const Fp& ext_ninv, const Fp& zeta_inv) {
-  long ext_n = 1L << ext_k;
-  hipMemcpyAsync(pd.ws0, ext_in, ext_n * sizeof(Fp), hipMemcpyHostToDevice, c->stream);
-  auto noprof = [&](int) { return 0; };
-  if (ntt_run(pd.ws0, pd.ws1, pd.plan_ext, ext_k, true, c->stream, &ext_ninv, noprof) !=
-      hipSuccess)
-    return TG_ERR_HIP;
-  coset_scale_launch(pd.ws0, (u64)ext_n, zeta_inv, c->stream);
-  hipMemcpyAsync(coeff_out, pd.ws0, ext_n * sizeof(Fp), hipMemcpyDeviceToHost, c->stream);
-  return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : TG_ERR_HIP;
 }
 
 // Batched GPU MSM: B same-size MSMs (nn points each) over ONE device base
@@ -162,45 +142,21 @@ static int gpu_msm_commit_batch(Ctx* c, ProverDev& pd, const Fp* mont_scalars, l
                      (Fp*)c->d_scalars, pd.sc_stage, (u64)ntot);
   ProfScope total(c, P_MSM_TOTAL);
   MsmCfg cfg = msm_cfg(nn);
-  u64 m = (u64)cfg.nwin * cfg.nbuck * (u64)B;
-  hipMemsetAsync(c->msm.d_hist, 0, m * 4, c->stream);
-  hipLaunchKernelGGL(k_digits, dim3(msm_grid(ntot)), dim3(256), 0, c->stream,
-                     c->d_scalars, (u64)ntot, (u64)nn, cfg, c->msm.d_dig, c->msm.d_hist);
-  msm_scan(c->msm.d_hist, c->msm.d_off, c->msm.d_bsum, m, c->stream);
-  hipMemcpyAsync(c->msm.d_hist, c->msm.d_off, m * 4, hipMemcpyDeviceToDevice, c->stream);
-  hipLaunchKernelGGL(k_scatter, dim3(msm_grid(ntot)), dim3(256), 0, c->stream,
-                     c->msm.d_dig, (u64)ntot, (u64)nn, cfg, c->msm.d_off, c->msm.d_sorted);
-  hipMemcpyAsync(c->msm.d_end, c->msm.d_off, m * 4, hipMemcpyDeviceToDevice, c->stream);
-  hipMemsetAsync(c->msm.d_big + m, 0, 4, c->stream);
-  const uint32_t* ord = msm_len_sort(c->msm, cfg, m, c->stream);
-  {
-    ProfScope p(c, P_MSM_ACC);
-    hipLaunchKernelGGL(k_bucket_acc<false>, dim3(msm_grid(m)), dim3(256), 0, c->stream,
-                       c->msm.d_hist, c->msm.d_end, c->msm.d_sorted, d_bases,
-                       c->msm.d_buckets, m, c->msm.d_big, c->msm.d_big + m, ord);
-    hipLaunchKernelGGL(k_bucket_acc_big<false>, dim3(1024), dim3(MSM_BIG_LANES), 0, c->stream,
-                       c->msm.d_hist, c->msm.d_end, c->msm.d_sorted, d_bases,
-                       c->msm.d_buckets, c->msm.d_big, c->msm.d_big + m);
-  }
-  hipLaunchKernelGGL(k_bucket_reduce, dim3(msm_grid((u64)cfg.nwin * B * cfg.nseg)),
-                     dim3(256), 0, c->stream, c->msm.d_buckets, c->msm.d_partials,
-                     (u64)cfg.nwin * B, cfg);
-  hipLaunchKernelGGL(k_wsum, dim3(cfg.nwin * B), dim3(256), 0, c->stream,
-                     c->msm.d_partials, c->msm.d_wsums, cfg);
   std::vector<VestaJac> wsums((size_t)cfg.nwin * B);
-  hipMemcpyAsync(wsums.data(), c->msm.d_wsums, sizeof(VestaJac) * wsums.size(),
-                 hipMemcpyDeviceToHost, c->stream);
+  // only the two accumulation kernels are bracketed here (bench.py reads
+  // msm_bucket_acc with profiling on; more event records would sit inside
+  // its timed region)
+  auto prof = [&](int idx) {
+    return ProfScope(c, idx == MSM_P_ACC_KERNELS ? (int)P_MSM_ACC : -1);
+  };
+  msm_run(c->msm, c->d_scalars, (u64)ntot, (u64)nn, (u64)B, d_bases, false, c->stream,
+          wsums.data(), prof);
   if (hipStreamSynchronize(c->stream) != hipSuccess) return TG_ERR_HIP;
 #ifdef _OPENMP
 #pragma omp parallel for schedule(static)
 #endif
   for (int b = 0; b < B; b++) {
-    VestaJac acc = jac_identity<FqCfg>();
-    for (int w = cfg.nwin - 1; w >= 0; w--) {
-      if (w != cfg.nwin - 1)
-        for (int d2 = 0; d2 < cfg.c; d2++) acc = jac_dbl(acc);
-      acc = jac_add(acc, wsums[(size_t)b * cfg.nwin + w]);
-    }
+    VestaJac acc = msm_host_combine_jac(wsums.data() + (size_t)b * cfg.nwin, cfg);
     if (!fd_is_zero(blinds[b])) acc = jac_add(acc, wtab->mul(blinds[b]));
     outs[b] = jac_to_aff(acc);
   }
@@ -1291,9 +1247,8 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   {
     // iNTT + zeta-undistribute directly on the device h buffer
     Fp* dH = pdev_ext_buf(pd, EB_H);
-    auto noprof = [&](int) { return 0; };
     if (ntt_run(dH, pd.ws1, pd.plan_ext, d.ext_k, true, c->stream, &pk.ext_n_inv,
-                noprof) != hipSuccess)
+                ntt_noprof) != hipSuccess)
       return TG_ERR_HIP;
     coset_scale_launch(dH, (u64)ext_n, pk.zeta_inv, c->stream);
     hipMemcpyAsync(h_coeff.data(), dH, ext_n * sizeof(Fp), hipMemcpyDeviceToHost,
@@ -1659,11 +1614,7 @@ static int pprove_raw(Ctx* c, PPk& pk, const uint8_t* instance, const uint8_t* a
   for (int r = 0; r < d.n_instance_rows; r++) {
     Fp v;
     memcpy(v.l, instance + 32 * r, 32);
-    for (int limb = 3;; limb--) {
-      if (v.l[limb] > FpCfg::MOD[limb]) return TG_ERR_ENCODING;
-      if (v.l[limb] < FpCfg::MOD[limb]) break;
-      if (limb == 0) return TG_ERR_ENCODING;
-    }
+    if (!fd_is_canonical(v)) return TG_ERR_ENCODING;
     inst_lag[r] = fd_to_mont(v);
   }
   std::vector<std::vector<Fp>> advice_lag(d.n_advice, std::vector<Fp>(n));
@@ -1675,11 +1626,7 @@ static int pprove_raw(Ctx* c, PPk& pk, const uint8_t* instance, const uint8_t* a
     for (long i = 0; i < n; i++) {
       Fp v;
       memcpy(v.l, advice + ((size_t)col * n + i) * 32, 32);
-      for (int limb = 3;; limb--) {
-        if (v.l[limb] > FpCfg::MOD[limb]) { bad |= 1; break; }
-        if (v.l[limb] < FpCfg::MOD[limb]) break;
-        if (limb == 0) { bad |= 1; break; }
-      }
+      if (!fd_is_canonical(v)) bad |= 1;
       advice_lag[col][i] = fd_to_mont(v);
     }
   }
@@ -2201,11 +2148,7 @@ static int pinst_from_raw(const PDesc& d, const uint8_t* instance,
   for (int r = 0; r < d.n_instance_rows; r++) {
     Fp v;
     memcpy(v.l, instance + 32 * r, 32);
-    for (int limb = 3;; limb--) {
-      if (v.l[limb] > FpCfg::MOD[limb]) return TG_ERR_ENCODING;
-      if (v.l[limb] < FpCfg::MOD[limb]) break;
-      if (limb == 0) return TG_ERR_ENCODING;
-    }
+    if (!fd_is_canonical(v)) return TG_ERR_ENCODING;
     inst_lag[r] = fd_to_mont(v);
   }
   return 0;

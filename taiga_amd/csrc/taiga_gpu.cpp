@@ -13,7 +13,9 @@
 #include <array>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "msm.hip"
@@ -21,7 +23,6 @@
 #include "poseidon.hip"
 #include "binding_sig.hpp"
 #include "tx_wire.hpp"
-#include "fd28.hpp"
 #include "witness.hpp"
 #include "prover_impl.hpp"
 #include "hf_rtc.hpp"
@@ -36,15 +37,7 @@ __global__ void __launch_bounds__(256) k_to_mont_check(Fd<C>* out, const Fd<C>* 
   for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n;
        i += (u64)gridDim.x * blockDim.x) {
     Fd<C> v = in[i];
-    bool lt = false;
-#pragma unroll
-    for (int limb = 3; limb >= 0; limb--) {
-      if (!lt) {
-        if (v.l[limb] > C::MOD[limb]) { atomicOr(err, 1u); break; }
-        if (v.l[limb] < C::MOD[limb]) lt = true;
-      }
-    }
-    if (!lt) atomicOr(err, 1u);
+    if (!fd_is_canonical(v)) atomicOr(err, 1u);
     out[i] = fd_to_mont(v);
   }
 }
@@ -66,20 +59,7 @@ __global__ void __launch_bounds__(256) k_aff_to_mont_check(VestaAff* out, const 
       out[i] = p;  // identity stays (0,0)
       continue;
     }
-    bool bad = false;
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-      const Fq& v = c ? p.y : p.x;
-      bool lt = false;
-#pragma unroll
-      for (int limb = 3; limb >= 0; limb--) {
-        if (!lt) {
-          if (v.l[limb] > FqCfg::MOD[limb]) { bad = true; break; }
-          if (v.l[limb] < FqCfg::MOD[limb]) lt = true;
-        }
-      }
-      if (!lt) bad = true;
-    }
+    bool bad = !fd_is_canonical(p.x) || !fd_is_canonical(p.y);
     VestaAff m;
     m.x = fd_to_mont(p.x);
     m.y = fd_to_mont(p.y);
@@ -108,16 +88,7 @@ __global__ void __launch_bounds__(256) k_decompress(VestaAff* out, const uint8_t
       continue;
     }
     Fq x{{l[0], l[1], l[2], l[3]}};
-    // canonical check
-    bool lt = false, bad = false;
-#pragma unroll
-    for (int limb = 3; limb >= 0; limb--) {
-      if (!lt) {
-        if (x.l[limb] > FqCfg::MOD[limb]) { bad = true; break; }
-        if (x.l[limb] < FqCfg::MOD[limb]) lt = true;
-      }
-    }
-    if (!lt) bad = true;
+    bool bad = !fd_is_canonical(x);
     Fq xm = fd_to_mont(x);
     Fq five{{5, 0, 0, 0}};
     Fq rhs = fd_add(fd_mul(fd_sqr(xm), xm), fd_to_mont(five));
@@ -203,11 +174,14 @@ static int tg_enter(Ctx* c) {
   return 0;
 }
 
+// idx < 0: a scope that records nothing (a launcher stage the caller does
+// not profile)
 struct ProfScope {
   Ctx* c;
   int idx;
-  ProfScope(Ctx* c_, int idx_) : c(c_), idx(idx_) {
-    if (c->prof) {
+  bool on;
+  ProfScope(Ctx* c_, int idx_) : c(c_), idx(idx_), on(c_->prof && idx_ >= 0) {
+    if (on) {
       hipEvent_t ev;
       hipEventCreate(&ev);
       hipEventRecord(ev, c->stream);
@@ -215,7 +189,7 @@ struct ProfScope {
     }
   }
   ~ProfScope() {
-    if (c->prof) {
+    if (on) {
       hipEvent_t ev;
       hipEventCreate(&ev);
       hipEventRecord(ev, c->stream);
@@ -235,6 +209,124 @@ enum {
 #include "prover_gpu.inc"
 
 using namespace taiga;
+
+// ---------- host helpers shared by the entry points ----------
+
+// temporary device memory, freed on every way out of the scope
+template <class T>
+struct DevTmp {
+  T* p = nullptr;
+  DevTmp() = default;
+  DevTmp(const DevTmp&) = delete;
+  DevTmp& operator=(const DevTmp&) = delete;
+  ~DevTmp() {
+    if (p) hipFree(p);
+  }
+  hipError_t alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)); }
+};
+
+// the 4-byte device flag the ingestion kernels OR their verdict into
+static hipError_t err_flag_new(DevTmp<unsigned>& f, hipStream_t stream) {
+  hipError_t e = f.alloc(1);
+  return e != hipSuccess ? e : hipMemsetAsync(f.p, 0, 4, stream);
+}
+
+// enqueue its read-back (valid after the stream is synchronized)
+static void err_flag_read(const DevTmp<unsigned>& f, unsigned* host, hipStream_t stream) {
+  hipMemcpyAsync(host, f.p, 4, hipMemcpyDeviceToHost, stream);
+}
+
+static int emit_proof(const std::vector<uint8_t>& proof, uint8_t* out, size_t cap,
+                      size_t* out_len) {
+  if (proof.size() > cap) return TG_ERR_BADARG;
+  memcpy(out, proof.data(), proof.size());
+  *out_len = proof.size();
+  return TG_OK;
+}
+
+// batch-verification weights: rho_0 = 1, rho_i = DRBG(Blake2b(parts...))
+// field draws. The caller chooses what the batch hash covers, in order.
+static std::vector<Fp> batch_rho(
+    size_t m, std::initializer_list<std::pair<const void*, size_t>> parts) {
+  std::vector<Fp> rho(m);
+  rho[0] = fd_one_mont<FpCfg>();
+  if (m > 1) {
+    Blake2b h(32, (const uint8_t*)"TaigaGPU-BatchVf");
+    for (const auto& part : parts) h.update((const uint8_t*)part.first, part.second);
+    uint8_t seed[32];
+    h.final(seed);
+    Drbg rng(seed);
+    for (size_t i = 1; i < m; i++) rho[i] = rng.field<FpCfg>();
+  }
+  return rho;
+}
+
+/* expand the 192-byte borsh CompliancePublicInputs block into the real
+ * 9 instance rows [nf, anchor, cm, delta_x, delta_y, rlcm halves]
+ * (compliance.rs to_instance order; closes the round-1 placeholder
+ * mapping flagged in ADVICE.md item 3) */
+static bool compliance_rows_expand(const uint8_t* inst192, uint8_t rows[288]) {
+  memcpy(rows, inst192 + 32, 32);       // nf
+  memcpy(rows + 32, inst192, 32);       // anchor
+  memcpy(rows + 64, inst192 + 64, 32);  // cm
+  bool all0 = true;
+  for (int b = 0; b < 32; b++)
+    if (inst192[96 + b]) all0 = false;
+  if (all0) {
+    memset(rows + 96, 0, 64);
+  } else {
+    PallasJac d;
+    if (!pallas_decompress(d, inst192 + 96)) return false;
+    PallasAff a = jac_to_aff(d);
+    Fp x = fd_from_mont(a.x), y = fd_from_mont(a.y);
+    memcpy(rows + 96, x.l, 32);
+    memcpy(rows + 128, y.l, 32);
+  }
+  for (int half = 0; half < 2; half++) {
+    memset(rows + 160 + 64 * half, 0, 64);
+    memcpy(rows + 160 + 64 * half, inst192 + 128 + 32 * half, 16);
+    memcpy(rows + 192 + 64 * half + 0, inst192 + 128 + 32 * half + 16, 16);
+  }
+  return true;
+}
+
+// a key's verifying-key bytes as embedded in the wire formats: compressed
+// fixed commitments, then compressed sigma commitments
+static std::vector<uint8_t> pk_vk_bytes(const PPk* k) {
+  std::vector<uint8_t> out;
+  uint8_t b[32];
+  for (const auto* commits : {&k->fixed_commits, &k->sigma_commits})
+    for (const VestaAff& p : *commits) {
+      Transcript::compress(b, p);
+      out.insert(out.end(), b, b + 32);
+    }
+  return out;
+}
+
+// common tail of tg_compliance_prove / tg_rl_prove: run the attached
+// witness program on the parsed inputs, read the circuit-computed instance
+// rows into inst_rows (caller pre-fills the rows the circuit does not
+// compute), prove, emit the proof and the canonical instance rows
+static int witness_prove(Ctx* c, const std::vector<Fp>& inputs, std::vector<Fp>& inst_rows,
+                         const uint8_t rng_seed[32], uint8_t* proof_out, size_t cap,
+                         size_t* out_len, uint8_t* instance_out) {
+  PDesc& d = c->ppk->d;
+  std::vector<std::vector<Fp>> advice_lag;
+  if (!c->ppk->tgw.run_mont(inputs, d.n_advice, advice_lag)) return TG_ERR_BADARG;
+  c->ppk->tgw.read_instance_mont(advice_lag, inst_rows);
+  std::vector<Fp> inst_lag(d.n, fd_zero<FpCfg>());
+  std::copy(inst_rows.begin(), inst_rows.end(), inst_lag.begin());
+  std::vector<uint8_t> proof;
+  int rc = pprove_core(c, *c->ppk, inst_lag, advice_lag, rng_seed, proof);
+  if (rc != 0) return rc;
+  if ((rc = emit_proof(proof, proof_out, cap, out_len)) != TG_OK) return rc;
+  if (instance_out)
+    for (size_t r = 0; r < inst_rows.size(); r++) {
+      Fp v = fd_from_mont(inst_rows[r]);
+      memcpy(instance_out + 32 * r, v.l, 32);
+    }
+  return TG_OK;
+}
 
 extern "C" {
 
@@ -266,7 +358,6 @@ int tg_init(int device, tg_ctx** out) {
 void tg_destroy(tg_ctx* ctx) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return;
-  if (!c) return;
   hipStreamSynchronize(c->stream);
   for (PPk* pk : c->ppk_slots) {
     pdev_free(pk->pd);
@@ -376,30 +467,26 @@ int tg_load_srs(tg_ctx* ctx, const uint8_t* bytes, size_t len) {
     return set_err(c, "srs alloc g", e);
   if ((e = hipMalloc(&c->d_gl, n * sizeof(VestaAff))) != hipSuccess)
     return set_err(c, "srs alloc gl", e);
-  uint8_t* d_comp = nullptr;
-  unsigned* d_err = nullptr;
-  if ((e = hipMalloc(&d_comp, 2 * n * 32 + 64)) != hipSuccess)
+  DevTmp<uint8_t> d_comp;
+  DevTmp<VestaAff> d_wu;  // w and u, decompressed on device, copied to host
+  DevTmp<unsigned> d_err;
+  if ((e = d_comp.alloc(2 * n * 32 + 64)) != hipSuccess)
     return set_err(c, "srs alloc comp", e);
-  hipMalloc(&d_err, 4);
-  hipMemsetAsync(d_err, 0, 4, c->stream);
-  hipMemcpyAsync(d_comp, bytes + 4, 2 * n * 32 + 64, hipMemcpyHostToDevice, c->stream);
+  if ((e = d_wu.alloc(2)) != hipSuccess) return set_err(c, "srs alloc wu", e);
+  if ((e = err_flag_new(d_err, c->stream)) != hipSuccess)
+    return set_err(c, "srs alloc err", e);
+  hipMemcpyAsync(d_comp.p, bytes + 4, 2 * n * 32 + 64, hipMemcpyHostToDevice, c->stream);
   hipLaunchKernelGGL(k_decompress, dim3(msm_grid(n)), dim3(256), 0, c->stream, c->d_g,
-                     d_comp, n, d_err);
+                     d_comp.p, n, d_err.p);
   hipLaunchKernelGGL(k_decompress, dim3(msm_grid(n)), dim3(256), 0, c->stream, c->d_gl,
-                     d_comp + n * 32, n, d_err);
-  // w and u: decompress on device into a scratch, copy to host Mont form
-  VestaAff* d_wu = nullptr;
-  hipMalloc(&d_wu, 2 * sizeof(VestaAff));
-  hipLaunchKernelGGL(k_decompress, dim3(1), dim3(64), 0, c->stream, d_wu,
-                     d_comp + 2 * n * 32, 2, d_err);
+                     d_comp.p + n * 32, n, d_err.p);
+  hipLaunchKernelGGL(k_decompress, dim3(1), dim3(64), 0, c->stream, d_wu.p,
+                     d_comp.p + 2 * n * 32, 2, d_err.p);
   unsigned h_err = 0;
-  hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, c->stream);
+  err_flag_read(d_err, &h_err, c->stream);
   VestaAff h_wu[2];
-  hipMemcpyAsync(h_wu, d_wu, 2 * sizeof(VestaAff), hipMemcpyDeviceToHost, c->stream);
+  hipMemcpyAsync(h_wu, d_wu.p, 2 * sizeof(VestaAff), hipMemcpyDeviceToHost, c->stream);
   e = hipStreamSynchronize(c->stream);
-  hipFree(d_comp);
-  hipFree(d_wu);
-  hipFree(d_err);
   if (e != hipSuccess) return set_err(c, "srs decompress", e);
   if (h_err) return TG_ERR_ENCODING;
   c->h_w = h_wu[0];
@@ -424,20 +511,17 @@ int tg_bases_upload(tg_ctx* ctx, const uint8_t* points_xy, size_t n) {
   if (!c->d_bases &&
       (e = hipMalloc(&c->d_bases, n * sizeof(VestaAff))) != hipSuccess)
     return set_err(c, "bases alloc", e);
-  VestaAff* d_raw = nullptr;
-  unsigned* d_err = nullptr;
-  if ((e = hipMalloc(&d_raw, n * sizeof(VestaAff))) != hipSuccess)
-    return set_err(c, "bases raw alloc", e);
-  hipMalloc(&d_err, 4);
-  hipMemsetAsync(d_err, 0, 4, c->stream);
-  hipMemcpyAsync(d_raw, points_xy, n * 64, hipMemcpyHostToDevice, c->stream);
+  DevTmp<VestaAff> d_raw;
+  DevTmp<unsigned> d_err;
+  if ((e = d_raw.alloc(n)) != hipSuccess) return set_err(c, "bases raw alloc", e);
+  if ((e = err_flag_new(d_err, c->stream)) != hipSuccess)
+    return set_err(c, "bases err alloc", e);
+  hipMemcpyAsync(d_raw.p, points_xy, n * 64, hipMemcpyHostToDevice, c->stream);
   hipLaunchKernelGGL(k_aff_to_mont_check, dim3(msm_grid(n)), dim3(256), 0, c->stream,
-                     c->d_bases, d_raw, n, d_err);
+                     c->d_bases, d_raw.p, n, d_err.p);
   unsigned h_err = 0;
-  hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, c->stream);
+  err_flag_read(d_err, &h_err, c->stream);
   e = hipStreamSynchronize(c->stream);
-  hipFree(d_raw);
-  hipFree(d_err);
   if (e != hipSuccess) return set_err(c, "bases upload", e);
   if (h_err) return TG_ERR_ENCODING;
   c->n_bases = n;
@@ -468,14 +552,12 @@ int tg_bases_download(tg_ctx* ctx, size_t n, uint8_t* out_xy) {
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
   if (!n || !c->d_bases || c->n_bases < n) return TG_ERR_BADARG;
   hipError_t e;
-  Fq* tmp = nullptr;
-  if ((e = hipMalloc(&tmp, n * sizeof(VestaAff))) != hipSuccess)
-    return set_err(c, "bases dl alloc", e);
+  DevTmp<Fq> tmp;
+  if ((e = tmp.alloc(2 * n)) != hipSuccess) return set_err(c, "bases dl alloc", e);
   hipLaunchKernelGGL(k_from_mont<FqCfg>, dim3(ntt_grid(2 * n)), dim3(256), 0, c->stream,
-                     tmp, (const Fq*)c->d_bases, (u64)(2 * n));
-  hipMemcpyAsync(out_xy, tmp, n * 64, hipMemcpyDeviceToHost, c->stream);
+                     tmp.p, (const Fq*)c->d_bases, (u64)(2 * n));
+  hipMemcpyAsync(out_xy, tmp.p, n * 64, hipMemcpyDeviceToHost, c->stream);
   e = hipStreamSynchronize(c->stream);
-  hipFree(tmp);
   return e == hipSuccess ? TG_OK : set_err(c, "bases dl", e);
 }
 
@@ -511,63 +593,13 @@ static int msm_common(Ctx* c, size_t n, int base_set, uint8_t out_xy[64]) {
   hipError_t e;
   if ((e = msm_work_alloc(c->msm, n)) != hipSuccess) return set_err(c, "msm ws", e);
   MsmCfg cfg = msm_cfg((long)n);
-  {
-    ProfScope total(c, P_MSM_TOTAL);
-    u64 m = (u64)cfg.nwin * cfg.nbuck;
-    {
-      ProfScope p(c, P_MSM_DIGITS);
-      hipMemsetAsync(c->msm.d_hist, 0, m * 4, c->stream);
-      hipLaunchKernelGGL(k_digits, dim3(msm_grid(n)), dim3(256), 0, c->stream,
-                         c->d_scalars, n, n, cfg, c->msm.d_dig, c->msm.d_hist);
-    }
-    {
-      ProfScope p(c, P_MSM_SCAN);
-      msm_scan(c->msm.d_hist, c->msm.d_off, c->msm.d_bsum, m, c->stream);
-      hipMemcpyAsync(c->msm.d_hist, c->msm.d_off, m * 4, hipMemcpyDeviceToDevice,
-                     c->stream);
-    }
-    {
-      ProfScope p(c, P_MSM_SCATTER);
-      hipLaunchKernelGGL(k_scatter, dim3(msm_grid(n)), dim3(256), 0, c->stream,
-                         c->msm.d_dig, n, n, cfg, c->msm.d_off, c->msm.d_sorted);
-      hipMemcpyAsync(c->msm.d_end, c->msm.d_off, m * 4, hipMemcpyDeviceToDevice,
-                     c->stream);
-    }
-    {
-      ProfScope p(c, P_MSM_ACC);
-      hipMemsetAsync(c->msm.d_big + m, 0, 4, c->stream);
-      const uint32_t* ord = msm_len_sort(c->msm, cfg, m, c->stream);
-      if (safe) {
-        hipLaunchKernelGGL(k_bucket_acc<true>, dim3(msm_grid(m)), dim3(256), 0, c->stream,
-                           c->msm.d_hist, c->msm.d_end, c->msm.d_sorted, bases,
-                           c->msm.d_buckets, m, c->msm.d_big, c->msm.d_big + m, ord);
-        hipLaunchKernelGGL(k_bucket_acc_big<true>, dim3(1024), dim3(MSM_BIG_LANES), 0, c->stream,
-                           c->msm.d_hist, c->msm.d_end, c->msm.d_sorted, bases,
-                           c->msm.d_buckets, c->msm.d_big, c->msm.d_big + m);
-      } else {
-        hipLaunchKernelGGL(k_bucket_acc<false>, dim3(msm_grid(m)), dim3(256), 0, c->stream,
-                           c->msm.d_hist, c->msm.d_end, c->msm.d_sorted, bases,
-                           c->msm.d_buckets, m, c->msm.d_big, c->msm.d_big + m, ord);
-        hipLaunchKernelGGL(k_bucket_acc_big<false>, dim3(1024), dim3(MSM_BIG_LANES), 0, c->stream,
-                           c->msm.d_hist, c->msm.d_end, c->msm.d_sorted, bases,
-                           c->msm.d_buckets, c->msm.d_big, c->msm.d_big + m);
-      }
-    }
-    {
-      ProfScope p(c, P_MSM_REDUCE);
-      hipLaunchKernelGGL(k_bucket_reduce, dim3(msm_grid((u64)cfg.nwin * cfg.nseg)),
-                         dim3(256), 0, c->stream, c->msm.d_buckets, c->msm.d_partials,
-                         (u64)cfg.nwin, cfg);
-    }
-    {
-      ProfScope p(c, P_MSM_WSUM);
-      hipLaunchKernelGGL(k_wsum, dim3(cfg.nwin), dim3(256), 0, c->stream,
-                         c->msm.d_partials, c->msm.d_wsums, cfg);
-    }
-  }
   VestaJac wsums[32]; /* nwin <= 32 (c >= 8) */
-  hipMemcpyAsync(wsums, c->msm.d_wsums, sizeof(VestaJac) * cfg.nwin,
-                 hipMemcpyDeviceToHost, c->stream);
+  // all six stages + total; the accumulation scope covers the length sort
+  static const int MSM_PROF_MAP[8] = {P_MSM_DIGITS, P_MSM_SCAN,   P_MSM_SCATTER,
+                                      P_MSM_ACC,    P_MSM_REDUCE, P_MSM_WSUM,
+                                      -1,           P_MSM_TOTAL};
+  auto prof = [&](int idx) { return ProfScope(c, MSM_PROF_MAP[idx]); };
+  msm_run(c->msm, c->d_scalars, n, n, 1, bases, safe, c->stream, wsums, prof);
   hipError_t es = hipStreamSynchronize(c->stream);
   if (es != hipSuccess) return set_err(c, "msm run", es);
   VestaAff r = msm_host_combine(wsums, cfg);
@@ -612,17 +644,16 @@ int tg_poly_upload(tg_ctx* ctx, const uint8_t* poly, uint32_t k) {
       return set_err(c, "poly tmp alloc", e);
     c->poly_k = (int)k;
   }
-  unsigned* d_err = nullptr;
-  hipMalloc(&d_err, 4);
-  hipMemsetAsync(d_err, 0, 4, c->stream);
+  DevTmp<unsigned> d_err;
+  if ((e = err_flag_new(d_err, c->stream)) != hipSuccess)
+    return set_err(c, "poly err alloc", e);
   // upload canonical into tmp, convert to Mont into d_poly
   hipMemcpyAsync(c->d_poly_tmp, poly, n * 32, hipMemcpyHostToDevice, c->stream);
   hipLaunchKernelGGL(k_to_mont_check<FpCfg>, dim3(ntt_grid(n)), dim3(256), 0, c->stream,
-                     c->d_poly, c->d_poly_tmp, n, d_err);
+                     c->d_poly, c->d_poly_tmp, n, d_err.p);
   unsigned h_err = 0;
-  hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, c->stream);
+  err_flag_read(d_err, &h_err, c->stream);
   e = hipStreamSynchronize(c->stream);
-  hipFree(d_err);
   if (e != hipSuccess) return set_err(c, "poly upload", e);
   if (h_err) return TG_ERR_ENCODING;
   return TG_OK;
@@ -678,10 +709,7 @@ int tg_ntt_fp(tg_ctx* ctx, int dir, uint32_t k, int coset, uint8_t* poly) {
   return tg_poly_download(ctx, poly, k);
 }
 
-}  // extern "C"
-
 /* ---- prover ABI (implementation in prover_gpu.inc) ---- */
-extern "C" {
 
 /* builds a proving key and caches it; returns the non-negative slot id
  * (also leaves it active for the slotless entry points). PKs are cached for
@@ -720,10 +748,7 @@ int tg_create_proof(tg_ctx* ctx, const uint8_t inst_seed[32], const uint8_t wit_
   std::vector<uint8_t> proof;
   int rc = pprove(c, *c->ppk, inst_seed, wit_seed, rng_seed, proof);
   if (rc != 0) return rc;
-  if (proof.size() > cap) return TG_ERR_BADARG;
-  memcpy(proof_out, proof.data(), proof.size());
-  *out_len = proof.size();
-  return TG_OK;
+  return emit_proof(proof, proof_out, cap, out_len);
 }
 
 int tg_witness_hash(tg_ctx* ctx, const uint8_t inst_seed[32], const uint8_t wit_seed[32],
@@ -751,10 +776,6 @@ int tg_witness_hash(tg_ctx* ctx, const uint8_t inst_seed[32], const uint8_t wit_
   h.final(out);
   return TG_OK;
 }
-
-}  /* extern "C" */
-
-extern "C" {
 
 int tg_verify_proof(tg_ctx* ctx, const uint8_t inst_seed[32], const uint8_t* proof,
                     size_t proof_len) {
@@ -800,20 +821,9 @@ int tg_verify_batch(tg_ctx* ctx, size_t m, const uint8_t* inst_seeds,
     if (rc != 0) return rc;
     off += proof_lens[i];
   }
-  /* weights: rho_0 = 1, rho_i = DRBG(Blake2b(seeds ‖ proofs)) field draws */
-  std::vector<Fp> rho(m);
-  rho[0] = fd_one_mont<FpCfg>();
-  if (m > 1) {
-    Blake2b h(32, (const uint8_t*)"TaigaGPU-BatchVf");
-    uint64_t mle = (uint64_t)m;
-    h.update((const uint8_t*)&mle, 8);
-    h.update(inst_seeds, 32 * m);
-    h.update(proofs, off);
-    uint8_t seed[32];
-    h.final(seed);
-    Drbg rng(seed);
-    for (size_t i = 1; i < m; i++) rho[i] = rng.field<FpCfg>();
-  }
+  /* weights over Blake2b(m ‖ seeds ‖ proofs) */
+  uint64_t mle = (uint64_t)m;
+  std::vector<Fp> rho = batch_rho(m, {{&mle, 8}, {inst_seeds, 32 * m}, {proofs, off}});
   return pverify_eval(c, *c->ppk, gds.data(), (int)m, rho.data());
 }
 
@@ -838,44 +848,10 @@ int tg_verify_batch_raw(tg_ctx* ctx, size_t m, const uint8_t* instances,
     if (rc != 0) return rc;
     off += proof_lens[i];
   }
-  std::vector<Fp> rho(m);
-  rho[0] = fd_one_mont<FpCfg>();
-  if (m > 1) {
-    Blake2b h(32, (const uint8_t*)"TaigaGPU-BatchVf");
-    uint64_t mle = (uint64_t)m;
-    h.update((const uint8_t*)&mle, 8);
-    h.update(instances, inst_stride * m);
-    h.update(proofs, off);
-    uint8_t seed[32];
-    h.final(seed);
-    Drbg rng(seed);
-    for (size_t i = 1; i < m; i++) rho[i] = rng.field<FpCfg>();
-  }
+  uint64_t mle = (uint64_t)m;
+  std::vector<Fp> rho =
+      batch_rho(m, {{&mle, 8}, {instances, inst_stride * m}, {proofs, off}});
   return pverify_eval(c, *c->ppk, gds.data(), (int)m, rho.data());
-}
-
-/* experiment self-test (fd28.hpp — carry-chain-free radix-2^28
- * Montgomery multiply, round-2 kernel candidate): host-side evaluation of
- * out = a * b * 2^-280 mod p over canonical Fp bytes. The arithmetic is
- * host/device-shared TG_HD code, so this pins the device semantics
- * numerically without a GPU (tests/test_fd28.py). Not a product entry. */
-int tg_dbg_fd28_mul(const uint8_t a_bytes[32], const uint8_t b_bytes[32],
-                    uint8_t out[32]) {
-  Fp a, b;
-  memcpy(a.l, a_bytes, 32);
-  memcpy(b.l, b_bytes, 32);
-  auto canon = [](const Fp& v) {
-    for (int limb = 3; limb >= 0; limb--) {
-      if (v.l[limb] > FpCfg::MOD[limb]) return false;
-      if (v.l[limb] < FpCfg::MOD[limb]) return true;
-    }
-    return false;  // equal to p
-  };
-  if (!canon(a) || !canon(b)) return TG_ERR_ENCODING;
-  Fd28<FpCfg> r = fd28_mul(fd28_from<FpCfg>(a), fd28_from<FpCfg>(b));
-  Fp v = fd28_norm(r);
-  memcpy(out, v.l, 32);
-  return TG_OK;
 }
 
 /* ---- binding signatures + transaction digest (host-side wire layer,
@@ -960,21 +936,43 @@ int tg_tx_verify(tg_ctx* ctx, const uint8_t* tx, size_t len) {
     rc = pverify_guard(c, *c->ppk, inst_lag, st.proof_ptr[i], st.proof_len[i], gds[i]);
     if (rc) return rc;
   }
-  std::vector<Fp> rho(m);
-  rho[0] = fd_one_mont<FpCfg>();
-  if (m > 1) {
-    Blake2b h(32, (const uint8_t*)"TaigaGPU-BatchVf");
-    h.update(tx, len);
-    uint8_t seed[32];
-    h.final(seed);
-    Drbg rng(seed);
-    for (size_t i = 1; i < m; i++) rho[i] = rng.field<FpCfg>();
-  }
+  std::vector<Fp> rho = batch_rho(m, {{tx, len}});  // the tx alone, no count prefix
   return pverify_eval(c, *c->ppk, gds.data(), (int)m, rho.data());
 }
 
-static bool compliance_rows_expand(const uint8_t* inst192, uint8_t rows[288]);
-static std::vector<uint8_t> pk_vk_bytes(PPk* k);
+/* one combined batch check of scattered proofs on the ACTIVE key (insts =
+ * their raw instance blocks, concatenated); an empty group passes.
+ * TG_ERR_BADARG passes through, any other failure is -1. */
+static int verify_group(tg_ctx* ctx, const uint8_t* insts,
+                        const std::vector<const uint8_t*>& proof_ptr,
+                        const std::vector<size_t>& proof_len) {
+  if (proof_ptr.empty()) return TG_OK;
+  std::vector<uint8_t> proofs;
+  for (size_t i = 0; i < proof_ptr.size(); i++)
+    proofs.insert(proofs.end(), proof_ptr[i], proof_ptr[i] + proof_len[i]);
+  int rc = tg_verify_batch_raw(ctx, proof_ptr.size(), insts, proofs.data(),
+                               proof_len.data());
+  return rc == TG_OK || rc == TG_ERR_BADARG ? rc : -1;
+}
+
+/* common tail of tg_tx_verify_full / tg_ptx_verify: batch-verify the RL
+ * group (22-row instances) on slot_rl, then the compliance group (cinst =
+ * expanded 9-row instances) on slot_compliance */
+static int verify_rl_then_compliance(tg_ctx* ctx, int slot_rl, int slot_compliance,
+                                     const std::vector<const uint8_t*>& rl_inst,
+                                     const std::vector<const uint8_t*>& rl_proof,
+                                     const std::vector<size_t>& rl_len,
+                                     const std::vector<uint8_t>& cinst,
+                                     const std::vector<const uint8_t*>& c_proof,
+                                     const std::vector<size_t>& c_len) {
+  int rc = tg_select_key(ctx, slot_rl);
+  if (rc) return rc;
+  std::vector<uint8_t> insts;
+  for (const uint8_t* ip : rl_inst) insts.insert(insts.end(), ip, ip + 22 * 32);
+  if ((rc = verify_group(ctx, insts.data(), rl_proof, rl_len))) return rc;
+  if ((rc = tg_select_key(ctx, slot_compliance))) return rc;
+  return verify_group(ctx, cinst.data(), c_proof, c_len);
+}
 
 /* FULL transaction verification (round 2; supersedes tg_tx_verify's
  * compliance-only check — ADVICE.md item 2): borsh Transaction parse +
@@ -996,7 +994,7 @@ int tg_tx_verify_full(tg_ctx* ctx, int slot_compliance, int slot_rl,
   rc = tx_check(tx, len, vk_len, nullptr, nullptr, &st);
   if (rc) return rc;
   // vk match + consistency checks per sptx
-  std::vector<uint8_t> vk_ref = pk_vk_bytes(rlk);
+  const std::vector<uint8_t> vk_ref = pk_vk_bytes(rlk);
   for (const uint8_t* vkb : st.rl_vk_ptr)
     if (memcmp(vkb, vk_ref.data(), vk_len) != 0) return -207;
   st.sptx_comp_begin.push_back(st.n_compliance);
@@ -1027,34 +1025,9 @@ int tg_tx_verify_full(tg_ctx* ctx, int slot_compliance, int slot_rl,
       }
     }
   }
-  // batch-verify RL proofs (RL key active)
-  if (st.n_rl) {
-    std::vector<uint8_t> insts;
-    std::vector<uint8_t> proofs;
-    std::vector<size_t> lens;
-    for (uint32_t r = 0; r < st.n_rl; r++) {
-      insts.insert(insts.end(), st.rl_inst_ptr[r], st.rl_inst_ptr[r] + 22 * 32);
-      proofs.insert(proofs.end(), st.rl_proof_ptr[r],
-                    st.rl_proof_ptr[r] + st.rl_proof_len[r]);
-      lens.push_back(st.rl_proof_len[r]);
-    }
-    rc = tg_verify_batch_raw(ctx, st.n_rl, insts.data(), proofs.data(),
-                             lens.data());
-    if (rc) return rc == TG_ERR_BADARG ? rc : -1;
-  }
-  // batch-verify compliance proofs
-  rc = tg_select_key(ctx, slot_compliance);
-  if (rc) return rc;
-  if (st.n_compliance) {
-    std::vector<uint8_t> proofs;
-    for (uint32_t i = 0; i < st.n_compliance; i++)
-      proofs.insert(proofs.end(), st.proof_ptr[i],
-                    st.proof_ptr[i] + st.proof_len[i]);
-    rc = tg_verify_batch_raw(ctx, st.n_compliance, cinst.data(), proofs.data(),
-                             st.proof_len.data());
-    if (rc) return rc == TG_ERR_BADARG ? rc : -1;
-  }
-  return TG_OK;
+  return verify_rl_then_compliance(ctx, slot_rl, slot_compliance, st.rl_inst_ptr,
+                                   st.rl_proof_ptr, st.rl_proof_len, cinst, st.proof_ptr,
+                                   st.proof_len);
 }
 
 /* batched Poseidon P128Pow5T3 ConstantLength<L> hashing (GPU witness
@@ -1066,43 +1039,32 @@ int tg_poseidon_hash(tg_ctx* ctx, const uint8_t* msgs, size_t n, int L,
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
   if (!msgs || !out || n == 0 || L < 1 || L > 64) return TG_ERR_BADARG;
-  hipError_t e = hipSetDevice(c->device);
-  if (e != hipSuccess) return set_err(c, "hipSetDevice", e);
+  hipError_t e;
   if (!c->pos_ready) {
     if ((e = pos_upload_consts()) != hipSuccess)
       return set_err(c, "poseidon consts", e);
     c->pos_ready = true;
   }
-  Fp* d_in = nullptr;
-  Fp* d_out = nullptr;
-  unsigned* d_err = nullptr;
-  size_t in_bytes = n * (size_t)L * 32;
-  if ((e = hipMalloc(&d_in, in_bytes)) != hipSuccess) return TG_ERR_NOMEM;
-  if ((e = hipMalloc(&d_out, n * 32)) != hipSuccess) { hipFree(d_in); return TG_ERR_NOMEM; }
-  if ((e = hipMalloc(&d_err, 4)) != hipSuccess) { hipFree(d_in); hipFree(d_out); return TG_ERR_NOMEM; }
-  hipMemsetAsync(d_err, 0, 4, c->stream);
-  hipMemcpyAsync(d_in, msgs, in_bytes, hipMemcpyHostToDevice, c->stream);
+  DevTmp<Fp> d_in, d_out;
+  DevTmp<unsigned> d_err;
+  if (d_in.alloc(n * (size_t)L) != hipSuccess || d_out.alloc(n) != hipSuccess ||
+      err_flag_new(d_err, c->stream) != hipSuccess)
+    return TG_ERR_NOMEM;
+  hipMemcpyAsync(d_in.p, msgs, n * (size_t)L * 32, hipMemcpyHostToDevice, c->stream);
   u64 grid = (n + 255) / 256;
   if (grid > 16384) grid = 16384;
   hipLaunchKernelGGL(k_poseidon_hash, dim3(grid), dim3(256), 0, c->stream,
-                     d_out, d_in, (u64)n, L, d_err);
+                     d_out.p, d_in.p, (u64)n, L, d_err.p);
   unsigned h_err = 0;
-  hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, c->stream);
+  err_flag_read(d_err, &h_err, c->stream);
   std::vector<uint8_t> h_out(n * 32);
-  hipMemcpyAsync(h_out.data(), d_out, n * 32, hipMemcpyDeviceToHost, c->stream);
+  hipMemcpyAsync(h_out.data(), d_out.p, n * 32, hipMemcpyDeviceToHost, c->stream);
   e = hipStreamSynchronize(c->stream);
-  hipFree(d_in);
-  hipFree(d_out);
-  hipFree(d_err);
   if (e != hipSuccess) return set_err(c, "poseidon", e);
   if (h_err) return TG_ERR_ENCODING;
   memcpy(out, h_out.data(), n * 32);
   return TG_OK;
 }
-
-}  /* extern "C" */
-
-extern "C" {
 
 /* raw-witness proving (SURVEY §8b witness-blob shape): instance =
  * n_instance_rows x 32B canonical reprs; advice = n_advice x 2^k x 32B
@@ -1136,25 +1098,10 @@ int tg_compliance_prove(tg_ctx* ctx, const uint8_t* info_borsh, size_t len,
   if (d.n_instance_rows != 9 || c->ppk->tgw.n_inputs != 124) return TG_ERR_STATE;
   std::vector<Fp> inputs;
   if (!compliance_inputs(info_borsh, len, inputs)) return TG_ERR_ENCODING;
-  std::vector<std::vector<Fp>> advice_lag;
-  if (!c->ppk->tgw.run_mont(inputs, d.n_advice, advice_lag)) return TG_ERR_BADARG;
   std::vector<Fp> inst_rows(9, fd_zero<FpCfg>());
   inst_rows[1] = inputs[1];  // anchor from the blob
-  c->ppk->tgw.read_instance_mont(advice_lag, inst_rows);
-  std::vector<Fp> inst_lag(d.n, fd_zero<FpCfg>());
-  for (int r = 0; r < 9; r++) inst_lag[r] = inst_rows[r];
-  std::vector<uint8_t> proof;
-  int rc = pprove_core(c, *c->ppk, inst_lag, advice_lag, rng_seed, proof);
-  if (rc != 0) return rc;
-  if (proof.size() > cap) return TG_ERR_BADARG;
-  memcpy(proof_out, proof.data(), proof.size());
-  *out_len = proof.size();
-  if (instance_out)
-    for (int r = 0; r < 9; r++) {
-      Fp v = fd_from_mont(inst_rows[r]);
-      memcpy(instance_out + 32 * r, v.l, 32);
-    }
-  return TG_OK;
+  return witness_prove(c, inputs, inst_rows, rng_seed, proof_out, cap, out_len,
+                       instance_out);
 }
 
 /* drop-in TrivialRL prove (resource_logic_examples.rs get_verifying_info):
@@ -1173,29 +1120,14 @@ int tg_rl_prove(tg_ctx* ctx, const uint8_t* witness_borsh, size_t len,
   uint8_t pad[16 * 32];
   if (!rl_inputs(witness_borsh, len, pad_rseed, inputs, pad))
     return TG_ERR_ENCODING;
-  std::vector<std::vector<Fp>> advice_lag;
-  if (!c->ppk->tgw.run_mont(inputs, d.n_advice, advice_lag)) return TG_ERR_BADARG;
   std::vector<Fp> inst_rows(22, fd_zero<FpCfg>());
   for (int r = 0; r < 16; r++) {
     Fp v;
     memcpy(v.l, pad + 32 * r, 32);
     inst_rows[6 + r] = fd_to_mont(v);
   }
-  c->ppk->tgw.read_instance_mont(advice_lag, inst_rows);
-  std::vector<Fp> inst_lag(d.n, fd_zero<FpCfg>());
-  for (int r = 0; r < 22; r++) inst_lag[r] = inst_rows[r];
-  std::vector<uint8_t> proof;
-  int rc = pprove_core(c, *c->ppk, inst_lag, advice_lag, rng_seed, proof);
-  if (rc != 0) return rc;
-  if (proof.size() > cap) return TG_ERR_BADARG;
-  memcpy(proof_out, proof.data(), proof.size());
-  *out_len = proof.size();
-  if (instance_out)
-    for (int r = 0; r < 22; r++) {
-      Fp v = fd_from_mont(inst_rows[r]);
-      memcpy(instance_out + 32 * r, v.l, 32);
-    }
-  return TG_OK;
+  return witness_prove(c, inputs, inst_rows, rng_seed, proof_out, cap, out_len,
+                       instance_out);
 }
 
 /* synthesized-advice export for parity tests: runs the attached program on
@@ -1301,18 +1233,7 @@ int tg_ptx_build(tg_ctx* ctx, int slot_compliance, int slot_rl,
   // RL sets (inputs then outputs)
   rc = tg_select_key(ctx, slot_rl);
   if (rc) return rc;
-  PPk* rlk = c->ppk;
-  std::vector<uint8_t> vk_bytes;
-  for (const VestaAff& p : rlk->fixed_commits) {
-    uint8_t b[32];
-    Transcript::compress(b, p);
-    vk_bytes.insert(vk_bytes.end(), b, b + 32);
-  }
-  for (const VestaAff& p : rlk->sigma_commits) {
-    uint8_t b[32];
-    Transcript::compress(b, p);
-    vk_bytes.insert(vk_bytes.end(), b, b + 32);
-  }
+  const std::vector<uint8_t> vk_bytes = pk_vk_bytes(c->ppk);
   for (int grp = 0; grp < 2; grp++) {
     uint32_t cnt = grp == 0 ? n_in : n_out;
     uint32_t base = grp == 0 ? 0 : n_in;
@@ -1343,53 +1264,7 @@ int tg_ptx_build(tg_ctx* ctx, int slot_compliance, int slot_rl,
     out.insert(out.end(), b, b + 32);
   }
   put_u32(0);  // hints: empty
-  if (out.size() > cap) return TG_ERR_BADARG;
-  memcpy(ptx_out, out.data(), out.size());
-  *out_len = out.size();
-  return TG_OK;
-}
-
-/* expand the 192-byte borsh CompliancePublicInputs block into the real
- * 9 instance rows [nf, anchor, cm, delta_x, delta_y, rlcm halves]
- * (compliance.rs to_instance order; closes the round-1 placeholder
- * mapping flagged in ADVICE.md item 3) */
-static bool compliance_rows_expand(const uint8_t* inst192, uint8_t rows[288]) {
-  memcpy(rows, inst192 + 32, 32);       // nf
-  memcpy(rows + 32, inst192, 32);       // anchor
-  memcpy(rows + 64, inst192 + 64, 32);  // cm
-  bool all0 = true;
-  for (int b = 0; b < 32; b++)
-    if (inst192[96 + b]) all0 = false;
-  if (all0) {
-    memset(rows + 96, 0, 64);
-  } else {
-    PallasJac d;
-    if (!pallas_decompress(d, inst192 + 96)) return false;
-    PallasAff a = jac_to_aff(d);
-    Fp x = fd_from_mont(a.x), y = fd_from_mont(a.y);
-    memcpy(rows + 96, x.l, 32);
-    memcpy(rows + 128, y.l, 32);
-  }
-  for (int half = 0; half < 2; half++) {
-    memset(rows + 160 + 64 * half, 0, 64);
-    memcpy(rows + 160 + 64 * half, inst192 + 128 + 32 * half, 16);
-    memcpy(rows + 192 + 64 * half + 0, inst192 + 128 + 32 * half + 16, 16);
-  }
-  return true;
-}
-
-static std::vector<uint8_t> pk_vk_bytes(PPk* k) {
-  std::vector<uint8_t> out;
-  uint8_t b[32];
-  for (const VestaAff& p : k->fixed_commits) {
-    Transcript::compress(b, p);
-    out.insert(out.end(), b, b + 32);
-  }
-  for (const VestaAff& p : k->sigma_commits) {
-    Transcript::compress(b, p);
-    out.insert(out.end(), b, b + 32);
-  }
-  return out;
+  return emit_proof(out, ptx_out, cap, out_len);
 }
 
 /* verify one borsh ShieldedPartialTransaction end-to-end
@@ -1408,6 +1283,7 @@ int tg_ptx_verify(tg_ctx* ctx, int slot_compliance, int slot_rl,
   PPk* rlk = c->ppk;
   uint32_t vk_len = 32u * (uint32_t)(rlk->fixed_commits.size() +
                                      rlk->sigma_commits.size());
+  const std::vector<uint8_t> vk_ref = pk_vk_bytes(rlk);
   TxCursor cur{ptx, len};
   uint32_t n_cvi;
   if (!cur.u32(n_cvi) || n_cvi > 64) return -201;
@@ -1429,7 +1305,7 @@ int tg_ptx_verify(tg_ctx* ctx, int slot_compliance, int slot_rl,
     nfs.insert(nfs.end(), rows, rows + 32);
     cms.insert(cms.end(), rows + 64, rows + 96);
   }
-  uint32_t n_in, n_out;
+  uint32_t n_in = 0, n_out = 0;
   std::vector<const uint8_t*> rproof;
   std::vector<size_t> rplen;
   std::vector<const uint8_t*> rinst;
@@ -1441,8 +1317,6 @@ int tg_ptx_verify(tg_ctx* ctx, int slot_compliance, int slot_rl,
     for (uint32_t i = 0; i < cnt; i++) {
       const uint8_t* vkb;
       if (!cur.take(vkb, vk_len)) return -206;
-      static thread_local std::vector<uint8_t> vk_ref;
-      if (vk_ref.size() != vk_len) vk_ref = pk_vk_bytes(rlk);
       if (memcmp(vkb, vk_ref.data(), vk_len) != 0)
         return -207;  // unknown RL vk (only the TrivialRL key is loaded)
       uint32_t plen;
@@ -1476,29 +1350,10 @@ int tg_ptx_verify(tg_ctx* ctx, int slot_compliance, int slot_rl,
   for (uint32_t i = 0; i < n_out; i++)
     if (memcmp(self_ids.data() + 32ul * (n_in + i), cms.data() + 32ul * i, 32) != 0)
       return -304;
-  // batch-verify RL proofs on the RL key
-  {
-    std::vector<uint8_t> insts;
-    for (const uint8_t* ip : rinst) insts.insert(insts.end(), ip, ip + 22 * 32);
-    std::vector<uint8_t> proofs;
-    for (size_t i = 0; i < rproof.size(); i++)
-      proofs.insert(proofs.end(), rproof[i], rproof[i] + rplen[i]);
-    rc = tg_verify_batch_raw(ctx, rproof.size(), insts.data(), proofs.data(),
-                             rplen.data());
-    if (rc) return rc == TG_ERR_BADARG ? rc : -1;
-  }
-  // batch-verify compliance proofs on the compliance key
-  rc = tg_select_key(ctx, slot_compliance);
-  if (rc) return rc;
-  {
-    std::vector<uint8_t> proofs;
-    for (size_t i = 0; i < cproof.size(); i++)
-      proofs.insert(proofs.end(), cproof[i], cproof[i] + cplen[i]);
-    rc = tg_verify_batch_raw(ctx, cproof.size(), cinst.data(), proofs.data(),
-                             cplen.data());
-    if (rc) return rc == TG_ERR_BADARG ? rc : -1;
-  }
-  return TG_OK;
+  // no proofs at all is not a bundle this entry accepts
+  if (n_cvi == 0) return TG_ERR_BADARG;
+  return verify_rl_then_compliance(ctx, slot_rl, slot_compliance, rinst, rproof, rplen,
+                                   cinst, cproof, cplen);
 }
 
 int tg_create_proof_raw(tg_ctx* ctx, const uint8_t* instance, const uint8_t* advice,
@@ -1510,10 +1365,7 @@ int tg_create_proof_raw(tg_ctx* ctx, const uint8_t* instance, const uint8_t* adv
   std::vector<uint8_t> proof;
   int rc = pprove_raw(c, *c->ppk, instance, advice, rng_seed, proof);
   if (rc != 0) return rc;
-  if (proof.size() > cap) return TG_ERR_BADARG;
-  memcpy(proof_out, proof.data(), proof.size());
-  *out_len = proof.size();
-  return TG_OK;
+  return emit_proof(proof, proof_out, cap, out_len);
 }
 
 }  /* extern "C" */

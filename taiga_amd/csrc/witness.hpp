@@ -261,11 +261,7 @@ inline bool parse_resource(const uint8_t* p, ResourceB& r) {
   auto rd = [&](const uint8_t* q, Fp& out) {
     Fp v;
     memcpy(v.l, q, 32);
-    // canonicality: v < MOD
-    for (int i = 3; i >= 0; i--) {
-      if (v.l[i] < FpCfg::MOD[i]) break;
-      if (v.l[i] > FpCfg::MOD[i] || i == 0) return false;
-    }
+    if (!fd_is_canonical(v)) return false;
     out = fd_to_mont(v);
     return true;
   };

@@ -1,6 +1,7 @@
 // arith_probe.cpp — host-side probe of the product's __host__ __device__
-// arithmetic (pasta_device.hpp) and the host parts of msm.hip (msm_cfg,
-// msm_host_combine). TEST CODE: built and driven by tests/test_host_arith.py.
+// arithmetic (pasta_device.hpp), the host parts of msm.hip (msm_cfg,
+// msm_host_combine) and the fd28 experiment (tools/experiments/fd28.hpp).
+// TEST CODE: built and driven by tests/test_host_arith.py and test_fd28.py.
 //
 // Reads one operation per line from stdin, prints one line of hex results.
 // Calls no HIP runtime function, so it runs on a machine without a GPU.
@@ -9,7 +10,7 @@
 // are "<op> <p|q> <args...>":
 //   raw ops work on the limbs as given (what the kernels see):
 //     add a b | sub a b | neg a | mul a b | sqr a | tomont a | frommont a |
-//     isodd a | rt a
+//     isodd a | rt a | canon a   (canon prints 1 iff a < modulus)
 //   standard-form ops convert to Montgomery form, run, and convert back:
 //     inv a | pow a e(decimal u64) | sqrt a   (sqrt prints "<flag> [root]")
 // Curve lines (Vesta; every coordinate in standard form, converted here):
@@ -18,6 +19,8 @@
 //   aneg x y | anegf x y | j2a X Y Z   -> "x y"
 //   comb c nwin (X Y Z)*nwin           -> "x y"
 //   cfg n -> "c nwin nbuck nseg seg" ; consts -> the MSM_* constants
+// fd28 experiment (Fp): mul28 a b -> a*b*2^-280 mod p, or "NONCANONICAL" when
+//   an operand is not below p
 
 #include <cinttypes>
 #include <cstdio>
@@ -29,6 +32,7 @@
 
 #include "pasta_device.hpp"
 #include "msm.hip"
+#include "fd28.hpp"
 
 using namespace taiga;
 
@@ -83,6 +87,8 @@ static bool field_op(const std::vector<std::string>& t, std::string& out) {
     out = hex(fd_from_mont(fd_to_mont(a)));
   } else if (op == "isodd") {
     out = fd_is_odd_std(a) ? "1" : "0";
+  } else if (op == "canon") {
+    out = fd_is_canonical(a) ? "1" : "0";
   } else if (op == "inv") {
     out = hex(fd_from_mont(fd_inv(fd_to_mont(a))));
   } else if (op == "pow") {
@@ -190,6 +196,13 @@ int main() {
             std::to_string(MSM_NBUCK_MAX) + " " + std::to_string(MSM_SEG) + " " +
             std::to_string(MSM_BIG_BUCKET) + " " + std::to_string(MSM_BIG_LANES);
       ok = true;
+    } else if (t[0] == "mul28") {
+      Fp a, b;
+      ok = get(t, 1, a) && get(t, 2, b);
+      if (ok && fd_is_canonical(a) && fd_is_canonical(b))
+        out = hex(fd28_norm(fd28_mul(fd28_from<FpCfg>(a), fd28_from<FpCfg>(b))));
+      else
+        out = "NONCANONICAL";
     } else if (t.size() >= 3 && (t[1] == "p" || t[1] == "q")) {
       ok = t[1] == "p" ? field_op<FpCfg>(t, out) : field_op<FqCfg>(t, out);
     } else {

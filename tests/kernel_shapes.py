@@ -45,7 +45,7 @@ def expected_msm_c(n: int) -> int:
 
 
 def expected_msm_cfg(n: int) -> MsmCfg:
-    """What msm_cfg(n) answers with TG_MSM_SMALL_C / TG_MSM_SMALL_SEG unset."""
+    """What msm_cfg(n) answers."""
     return MSM_TABLE[expected_msm_c(n)]
 
 
@@ -77,8 +77,8 @@ NTT_MAX_GRID = 2048
 
 
 def expected_ntt_passes(k: int):
-    """Kernel sequence ntt_run() launches for a 2^k transform with the
-    default environment, as (name, grid_stride_loop_engaged)."""
+    """Kernel sequence ntt_run() launches for a 2^k transform, as
+    (name, grid_stride_loop_engaged)."""
     n = 1 << k
     out = []
     s = 1

@@ -33,13 +33,12 @@ def probe(tmp_path_factory):
     subprocess.run(
         [HIPCC, "-O2", "-std=c++17", "--offload-arch=gfx950",
          "-I", os.path.join(REPO, "taiga_amd", "csrc"),
+         "-I", os.path.join(REPO, "tools", "experiments"),
          os.path.join(REPO, "tests", "host", "arith_probe.cpp"), "-o", str(out)],
         check=True)
-    env = {k: v for k, v in os.environ.items()
-           if k not in ("TG_MSM_SMALL_C", "TG_MSM_SMALL_SEG")}
 
     def run(lines):
-        r = subprocess.run([str(out)], input="\n".join(lines) + "\n", env=env,
+        r = subprocess.run([str(out)], input="\n".join(lines) + "\n",
                            capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, (r.returncode, r.stdout[-200:], r.stderr[-200:])
         got = r.stdout.split("\n")[:-1]
@@ -105,6 +104,29 @@ def test_field_unary_ops(probe, f):
         cases.append((f"rt {f} {h(a)}", h(a), ("rt", a)))
         cases.append((f"isodd {f} {h(a)}", str(a * rinv % mod & 1), ("isodd", a)))
     check(probe, cases)
+
+
+@pytest.mark.parametrize("f", ["p", "q"])
+def test_field_is_canonical(probe, f):
+    """fd_is_canonical is the one input-range check of every decoder:
+    true iff the raw 256-bit value is below the modulus."""
+    mod = MODS[f]
+    limbs = [(mod >> (64 * i)) & (2**64 - 1) for i in range(4)]
+    assert all(l < 2**64 - 1 for l in limbs) and sum(1 for l in limbs if l) == 3
+    vals = [0, 1, mod - 1, mod, mod + 1, 2**254, 2**255, 2**256 - 1]
+    assert 2**254 < mod
+    for i in range(4):
+        vals.append(mod + (1 << (64 * i)))  # limb i raised by one
+        if limbs[i]:
+            vals.append(mod - (1 << (64 * i)))  # non-zero limb i lowered by one
+    vals += edge_values(mod)
+    rng = random.Random(71 if f == "p" else 72)
+    vals += [rng.getrandbits(256) for _ in range(2000)]
+    assert all(0 <= v < 2**256 for v in vals)
+    exp = [v < mod for v in vals]
+    assert sum(exp) > 100 and len(exp) - sum(exp) > 100
+    check(probe, [(f"canon {f} {h(v)}", "1" if e else "0", ("canon", v))
+                  for v, e in zip(vals, exp)])
 
 
 @pytest.mark.parametrize("f", ["p", "q"])

@@ -167,6 +167,62 @@ def test_gpu_ptx_ragged_parity(n, params15):
         g.close()
 
 
+RL_VK_LEN = 32 * (21 + 12)  # TrivialRL key: 21 fixed + 12 sigma commitments
+
+
+def _walk_ptx(ptx, vk_len=RL_VK_LEN):
+    """Offsets of the pieces of one borsh ShieldedPartialTransaction:
+    (compliance [(proof_off, proof_len, inst_off)], RL infos in wire order
+    [(vk_off, proof_off, proof_len, inst_off, is_input)])."""
+    import struct
+
+    (n_cvi,) = struct.unpack_from("<I", ptx, 0)
+    off = 4
+    comps, rls = [], []
+    for _ in range(n_cvi):
+        (plen,) = struct.unpack_from("<I", ptx, off)
+        comps.append((off + 4, plen, off + 4 + plen))
+        off += 4 + plen + 192
+    for grp in range(2):
+        (cnt,) = struct.unpack_from("<I", ptx, off)
+        off += 4
+        for _ in range(cnt):
+            vk_off = off
+            (plen,) = struct.unpack_from("<I", ptx, off + vk_len)
+            proof_off = vk_off + vk_len + 4
+            inst_off = proof_off + plen
+            rls.append((vk_off, proof_off, plen, inst_off, grp == 0))
+            (ndyn,) = struct.unpack_from("<I", ptx, inst_off + 22 * 32)
+            assert ndyn == 0
+            off = inst_off + 22 * 32 + 4
+    # Some(binding_sig_r) + empty hints vec close the bundle
+    assert ptx[off] == 1 and off + 1 + 32 + 4 == len(ptx)
+    return comps, rls
+
+
+def _ptx_structural_mutations(ptx):
+    """(label, mutated bundle, the code tg_ptx_verify answers) for bundles
+    that host-side parsing rejects before any kernel runs."""
+    comps, rls = _walk_ptx(ptx)
+    assert len(comps) == 2 and [r[4] for r in rls] == [True, True, False, False]
+
+    def flip(pos):
+        b = bytearray(ptx)
+        b[pos] ^= 1
+        return bytes(b)
+
+    first_in = next(r for r in rls if r[4])
+    first_out = next(r for r in rls if not r[4])
+    return [
+        ("one byte appended", ptx + b"\0", -214),
+        ("last byte dropped", ptx[:-1], -213),
+        ("first RL vk", flip(rls[0][0] + 5), -207),
+        ("second RL root", flip(rls[1][3] + 7), -301),
+        ("first input RL self id", flip(first_in[3] + 32 + 9), -303),
+        ("first output RL self id", flip(first_out[3] + 32 + 9), -304),
+    ]
+
+
 @pytest.mark.gpu
 def test_gpu_ptx_build_parity_and_verify(units, params15):
     import taiga_amd
@@ -200,6 +256,22 @@ def test_gpu_ptx_build_parity_and_verify(units, params15):
     bad = bytearray(ptx_gpu)
     bad[40] ^= 1  # inside the first compliance proof
     assert lib.tg_ptx_verify(g._h, slot_c, slot_r, bytes(bad), len(bad)) != 0
+    # structural and consistency rejections, each with its own code
+    for label, mut, want in _ptx_structural_mutations(ptx_gpu):
+        got = lib.tg_ptx_verify(g._h, slot_c, slot_r, mut, len(mut))
+        print(f"tg_ptx_verify [{label}] -> {got}")
+        assert got == want, (label, got, want)
+    # a second context on the same thread, keys generated in the other
+    # order: the bundle's RL vk bytes are compared with THAT context's key
+    g2 = taiga_amd.TaigaGpu(0)
+    try:
+        g2.load_srs(params15)
+        slot_r2 = g2.keygen(rdesc)
+        slot_c2 = g2.keygen(cdesc)
+        assert (slot_c2, slot_r2) != (slot_c, slot_r)
+        assert lib.tg_ptx_verify(g2._h, slot_c2, slot_r2, ptx_gpu, len(ptx_gpu)) == 0
+    finally:
+        g2.close()
     g.close()
 
 

@@ -100,9 +100,9 @@ __global__ void k3(Fd* out, const Fd* in, int n) {
   out[2*i] = r0; out[2*i+1] = r1;
 }
 
-// k4: the fd28 carry-chain-free Montgomery multiply (taiga_amd/csrc/
-// fd28.hpp) on the same workload shape as k1 — objdump slot comparison.
-#include "../../taiga_amd/csrc/fd28.hpp"
+// k4: the fd28 carry-chain-free Montgomery multiply (fd28.hpp) on the same
+// workload shape as k1 — objdump slot comparison.
+#include "fd28.hpp"
 using namespace taiga;
 __global__ void k4(Fd28<FpCfg>* out, const Fd28<FpCfg>* in, int n) {
   int i = blockIdx.x * 256 + threadIdx.x;

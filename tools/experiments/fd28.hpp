@@ -23,7 +23,7 @@
 // semantics up to compiler bugs; on-GPU A/B is round-2.
 #pragma once
 
-#include "pasta_device.hpp"
+#include "../../taiga_amd/csrc/pasta_device.hpp"
 
 namespace taiga {
 
