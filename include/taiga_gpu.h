@@ -260,6 +260,34 @@ void tg_prof_enable(tg_ctx* ctx, int on);
 void tg_prof_reset(tg_ctx* ctx);
 int tg_prof_get(tg_ctx* ctx, const char* name, double* total_ms, long* count);
 
+/* ---- diagnostics: the prover's opening-phase kernels on caller data ----
+ * Field elements are 32B LE canonical (TG_ERR_ENCODING otherwise); points
+ * are x||y canonical, the identity all-zero. Test entry points — the
+ * prover reaches the same kernels through tg_*_prove.
+ * tg_fp_poly_eval_batch: out[q] = sum_i coeffs[offs[q] + i] * points[q]^i,
+ *   i < lens[q]; nq queries over sub-ranges of one buffer, one launch.
+ * tg_fp_kate_div: divides the len coefficients by (X - points[0]), the
+ *   len-1 long quotient by (X - points[1]), and so on (remainders dropped);
+ *   coeffs returns the last quotient, zero from index len - npts on.
+ * tg_fp_horner_comb: out[i] = Horner over polys[0..np)[i] in challenge,
+ *   polys[0] taking the highest power; polys holds np vectors of n.
+ * tg_ipa_open_probe: the IPA opening rounds of poly (2^k coefficients) at
+ *   x3 over the first 2^k SRS bases, with caller-chosen round challenges
+ *   (k, non-zero) and round blinds (l, r per round: 2k). lr_out receives
+ *   L_j || R_j per round (128 B), a_out the final folded coefficient,
+ *   blind_out blind + sum_j (u_j * l_j + u_j^-1 * r_j). */
+int tg_fp_poly_eval_batch(tg_ctx* ctx, const uint8_t* coeffs, size_t n_coeffs,
+                          const uint64_t* offs, const uint64_t* lens,
+                          const uint8_t* points, size_t nq, uint8_t* out);
+int tg_fp_kate_div(tg_ctx* ctx, uint8_t* coeffs, size_t len, const uint8_t* points,
+                   size_t npts);
+int tg_fp_horner_comb(tg_ctx* ctx, const uint8_t* polys, size_t np, size_t n,
+                      const uint8_t challenge[32], uint8_t* out);
+int tg_ipa_open_probe(tg_ctx* ctx, uint32_t k, const uint8_t* poly, const uint8_t x3[32],
+                      const uint8_t* challenges, const uint8_t* round_blinds,
+                      const uint8_t blind[32], uint8_t* lr_out, uint8_t a_out[32],
+                      uint8_t blind_out[32]);
+
 /* ---- sync ---- */
 int tg_synchronize(tg_ctx* ctx);
 

@@ -127,6 +127,19 @@ def load_library():
             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
         ]
         lib.tg_synchronize.argtypes = [ctypes.c_void_p]
+        # diagnostics (opening-phase kernels on caller data)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        lib.tg_fp_poly_eval_batch.argtypes = [
+            ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, u64p, u64p,
+            ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
+        lib.tg_fp_kate_div.argtypes = [
+            ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
+            ctypes.c_size_t]
+        lib.tg_fp_horner_comb.argtypes = [
+            ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t,
+            ctypes.c_char_p, ctypes.c_char_p]
+        lib.tg_ipa_open_probe.argtypes = [
+            ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_char_p] * 8
         _lib = lib
     return _lib
 

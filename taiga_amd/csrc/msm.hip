@@ -47,9 +47,9 @@ inline MsmCfg msm_cfg(long n) {
     return MsmCfg{16, 16, 1 << 15, (1 << 15) / MSM_SEG, MSM_SEG};
   // below 2^18 the bucket space must track the MSM size (c ~ log2 n - 2,
   // floored at 8 to keep nwin <= 32 for the d_dig/d_wsums allocs): the prover's
-  // n=2^15 commits take c=13, the IPA's geometrically shrinking rounds
-  // smaller windows still. Reduce segments sized so nseg <= 1024 per
-  // window.
+  // n=2^15 commits and IPA rounds take c=13 (the rounds fold scalars over
+  // the original bases, so each is a full-n MSM), smaller MSMs smaller
+  // windows still. Reduce segments sized so nseg <= 1024 per window.
   int lg = 0;
   while ((1L << (lg + 1)) <= n) lg++;
   int sc = lg - 2 < 8 ? 8 : (lg - 2 > 13 ? 13 : lg - 2);

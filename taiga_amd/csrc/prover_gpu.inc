@@ -13,9 +13,57 @@ struct ProverDev {
   Fp* sc_stage = nullptr;  // batched-MSM scalar staging
   long sc_cap = 0;
   std::vector<Fp*> ext_pool;  // per-proof device ext buffers (h-fold inputs)
+  // opening phase (openings.hip): n-element slots holding the coefficient
+  // form of every per-proof polynomial the openings read, sized from the
+  // descriptor at keygen; the multiopen / IPA work vectors, sized when the
+  // number of point sets is first known; and the staging of the small
+  // per-launch tables and results
+  Fp* coef = nullptr;
+  int coef_slots = 0;
+  Fp* open_ws = nullptr;
+  int open_slots = 0;
+  void* d_stage = nullptr;
+  size_t stage_cap = 0;
+  Fp* d_small = nullptr;
+  size_t small_cap = 0;
   NttPlan plan_n, plan_ext;
   long ext_n = 0, n = 0;
 };
+
+// grow-only device buffer; the stream is drained before the old one goes
+template <class T>
+static T* pdev_grow(Ctx* c, T*& p, size_t& cap, size_t need) {
+  if (cap >= need) return p;
+  if (p) {
+    hipStreamSynchronize(c->stream);
+    hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  if (hipMalloc(&p, need * sizeof(T)) != hipSuccess) return nullptr;
+  cap = need;
+  return p;
+}
+
+static void* pdev_stage(Ctx* c, ProverDev& pd, size_t bytes) {
+  uint8_t* p = (uint8_t*)pd.d_stage;
+  p = pdev_grow(c, p, pd.stage_cap, std::max<size_t>(bytes, 16384));
+  pd.d_stage = p;
+  return p;
+}
+
+static Fp* pdev_small(Ctx* c, ProverDev& pd, size_t count) {
+  return pdev_grow(c, pd.d_small, pd.small_cap,
+                   std::max<size_t>(count, 2 * OPN_GRID_MAX));
+}
+
+// n-element slot arrays: (re)allocated only when more slots are needed
+static Fp* pdev_slots(Ctx* c, Fp*& p, int& have, int want, long n) {
+  size_t cap = (size_t)have * n;
+  Fp* r = pdev_grow(c, p, cap, (size_t)want * n);
+  have = (int)(cap / n);
+  return r;
+}
 
 static hipError_t pdev_init(Ctx* c, ProverDev& pd, int k, int ext_k) {
   long n = 1L << k, ext_n = 1L << ext_k;
@@ -44,6 +92,10 @@ static Fp* pdev_ext_buf(ProverDev& pd, size_t idx) {
 static void pdev_free(ProverDev& pd) {
   for (Fp* p : pd.ext_pool) hipFree(p);
   pd.ext_pool.clear();
+  if (pd.coef) hipFree(pd.coef);
+  if (pd.open_ws) hipFree(pd.open_ws);
+  if (pd.d_stage) hipFree(pd.d_stage);
+  if (pd.d_small) hipFree(pd.d_small);
   if (pd.d_hargs) hipFree(pd.d_hargs);
   if (pd.sc_stage) hipFree(pd.sc_stage);
   if (pd.ws0) hipFree(pd.ws0);
@@ -80,66 +132,52 @@ static int gpu_coeff_to_ext(Ctx* c, ProverDev& pd, const Fp* coeff, Fp* ext_out,
   return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : TG_ERR_HIP;
 }
 
-// fused: lagrange(host, Mont) -> coeff (host out) + extended-coset evals
-// left on device in d_ext_dst — one upload instead of two
-static int gpu_lag_to_coeff_ext_dev(Ctx* c, ProverDev& pd, Fp* host_lag_to_coeff,
-                                    Fp* d_ext_dst, int k, int ext_k, const Fp& ninv,
-                                    const Fp& zeta) {
+// fused: lagrange(host, Mont) -> coeff, left on device in the coefficient
+// pool slot d_coeff_dst (the openings read it there; it never returns to
+// the host) + extended-coset evals left on device in d_ext_dst
+static int gpu_lag_to_coeff_ext_dev(Ctx* c, ProverDev& pd, const Fp* host_lag,
+                                    Fp* d_coeff_dst, Fp* d_ext_dst, int k, int ext_k,
+                                    const Fp& ninv, const Fp& zeta) {
   long n = 1L << k, ext_n = 1L << ext_k;
-  hipMemcpyAsync(pd.ws0, host_lag_to_coeff, n * sizeof(Fp), hipMemcpyHostToDevice,
-                 c->stream);
+  hipMemcpyAsync(pd.ws0, host_lag, n * sizeof(Fp), hipMemcpyHostToDevice, c->stream);
   if (ntt_run(pd.ws0, pd.ws1, pd.plan_n, k, true, c->stream, &ninv, ntt_noprof) !=
       hipSuccess)
     return TG_ERR_HIP;
-  hipMemcpyAsync(host_lag_to_coeff, pd.ws0, n * sizeof(Fp), hipMemcpyDeviceToHost,
-                 c->stream);
+  hipMemcpyAsync(d_coeff_dst, pd.ws0, n * sizeof(Fp), hipMemcpyDeviceToDevice, c->stream);
   hipMemcpyAsync(d_ext_dst, pd.ws0, n * sizeof(Fp), hipMemcpyDeviceToDevice, c->stream);
   hipMemsetAsync(d_ext_dst + n, 0, (ext_n - n) * sizeof(Fp), c->stream);
   coset_scale_launch(d_ext_dst, (u64)ext_n, zeta, c->stream);
   if (ntt_run(d_ext_dst, pd.ws1, pd.plan_ext, ext_k, false, c->stream, nullptr,
               ntt_noprof) != hipSuccess)
     return TG_ERR_HIP;
-  return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : TG_ERR_HIP;
+  return 0;  // host_lag must outlive the stream's next synchronisation
 }
 
-// coeff(n, host) -> extended-coset evals left ON DEVICE in d_dst
-static int gpu_coeff_to_ext_dev(Ctx* c, ProverDev& pd, const Fp* coeff, Fp* d_dst, int k,
-                                int ext_k, const Fp& zeta) {
-  long n = 1L << k, ext_n = 1L << ext_k;
-  hipMemcpyAsync(d_dst, coeff, n * sizeof(Fp), hipMemcpyHostToDevice, c->stream);
-  hipMemsetAsync(d_dst + n, 0, (ext_n - n) * sizeof(Fp), c->stream);
-  coset_scale_launch(d_dst, (u64)ext_n, zeta, c->stream);
-  if (ntt_run(d_dst, pd.ws1, pd.plan_ext, ext_k, false, c->stream, nullptr,
-              ntt_noprof) != hipSuccess)
-    return TG_ERR_HIP;
+// workspace and the canonical-scalar array for B MSMs of nn points each
+static int gpu_msm_reserve(Ctx* c, long nn, int B) {
+  long ntot = nn * B;
+  if (msm_work_alloc(c->msm, (u64)ntot, (u64)B) != hipSuccess) return TG_ERR_NOMEM;
+  if (!c->d_scalars || c->n_scalars < (u64)ntot) {
+    if (c->d_scalars) {
+      hipStreamSynchronize(c->stream);
+      hipFree(c->d_scalars);
+      c->d_scalars = nullptr;
+    }
+    if (hipMalloc(&c->d_scalars, ntot * sizeof(ScalarRepr)) != hipSuccess)
+      return TG_ERR_NOMEM;
+    c->n_scalars = (u64)ntot;
+  }
   return 0;
 }
 
 // Batched GPU MSM: B same-size MSMs (nn points each) over ONE device base
-// array, one kernel chain. scalars = B concatenated Mont vectors. Each
-// result gets its blind*W added via the fixed-point table.
-static int gpu_msm_commit_batch(Ctx* c, ProverDev& pd, const Fp* mont_scalars, long nn,
-                                int B, const VestaAff* d_bases, const Fp* blinds,
-                                VestaAff* outs, const FixedMulTab* wtab) {
-  hipError_t e;
+// array, one kernel chain, from the B concatenated CANONICAL scalar vectors
+// already in c->d_scalars (gpu_msm_reserve'd). Each result gets its
+// blind*W added via the fixed-point table.
+static int gpu_msm_commit_canon(Ctx* c, long nn, int B, const VestaAff* d_bases,
+                                const Fp* blinds, VestaAff* outs,
+                                const FixedMulTab* wtab) {
   long ntot = nn * B;
-  if ((e = msm_work_alloc(c->msm, (u64)ntot, (u64)B)) != hipSuccess) return TG_ERR_NOMEM;
-  if (pd.sc_cap < ntot) {
-    if (pd.sc_stage) hipFree(pd.sc_stage);
-    if ((e = hipMalloc(&pd.sc_stage, ntot * sizeof(Fp))) != hipSuccess)
-      return TG_ERR_NOMEM;
-    pd.sc_cap = ntot;
-  }
-  hipMemcpyAsync(pd.sc_stage, mont_scalars, ntot * sizeof(Fp), hipMemcpyHostToDevice,
-                 c->stream);
-  if (!c->d_scalars || c->n_scalars < (u64)ntot) {
-    if (c->d_scalars) hipFree(c->d_scalars);
-    if ((e = hipMalloc(&c->d_scalars, ntot * sizeof(ScalarRepr))) != hipSuccess)
-      return TG_ERR_NOMEM;
-    c->n_scalars = (u64)ntot;
-  }
-  hipLaunchKernelGGL(k_from_mont<FpCfg>, dim3(ntt_grid(ntot)), dim3(256), 0, c->stream,
-                     (Fp*)c->d_scalars, pd.sc_stage, (u64)ntot);
   ProfScope total(c, P_MSM_TOTAL);
   MsmCfg cfg = msm_cfg(nn);
   std::vector<VestaJac> wsums((size_t)cfg.nwin * B);
@@ -161,6 +199,135 @@ static int gpu_msm_commit_batch(Ctx* c, ProverDev& pd, const Fp* mont_scalars, l
     outs[b] = jac_to_aff(acc);
   }
   return 0;
+}
+
+// the same from B concatenated Montgomery vectors already on the device
+static int gpu_msm_commit_batch_dev(Ctx* c, const Fp* d_mont_scalars, long nn, int B,
+                                    const VestaAff* d_bases, const Fp* blinds,
+                                    VestaAff* outs, const FixedMulTab* wtab) {
+  long ntot = nn * B;
+  int rc = gpu_msm_reserve(c, nn, B);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_from_mont<FpCfg>, dim3(ntt_grid(ntot)), dim3(256), 0, c->stream,
+                     (Fp*)c->d_scalars, d_mont_scalars, (u64)ntot);
+  return gpu_msm_commit_canon(c, nn, B, d_bases, blinds, outs, wtab);
+}
+
+// ... and from host Montgomery vectors: upload, then the device form
+static int gpu_msm_commit_batch(Ctx* c, ProverDev& pd, const Fp* mont_scalars, long nn,
+                                int B, const VestaAff* d_bases, const Fp* blinds,
+                                VestaAff* outs, const FixedMulTab* wtab) {
+  long ntot = nn * B;
+  size_t cap = (size_t)pd.sc_cap;
+  if (!pdev_grow(c, pd.sc_stage, cap, (size_t)ntot)) return TG_ERR_NOMEM;
+  pd.sc_cap = (long)cap;
+  hipMemcpyAsync(pd.sc_stage, mont_scalars, ntot * sizeof(Fp), hipMemcpyHostToDevice,
+                 c->stream);
+  return gpu_msm_commit_batch_dev(c, pd.sc_stage, nn, B, d_bases, blinds, outs, wtab);
+}
+
+// ---------------- opening-phase launchers (kernels: openings.hip) ---------
+// Each enqueues on the context's stream and returns; results the host needs
+// are valid after the caller's next stream synchronisation. The small
+// tables go through pd.d_stage: a later table's upload is stream-ordered
+// behind the kernel that reads the earlier one.
+
+// evs_host[q] = poly_q(x_q) for every query, one launch
+static int dev_poly_eval_batch(Ctx* c, ProverDev& pd, const std::vector<EvalQuery>& qs,
+                               Fp* evs_host) {
+  if (qs.empty()) return 0;
+  size_t nq = qs.size();
+  EvalQuery* dq = (EvalQuery*)pdev_stage(c, pd, nq * sizeof(EvalQuery));
+  Fp* dout = pdev_small(c, pd, nq);
+  if (!dq || !dout) return TG_ERR_NOMEM;
+  hipMemcpyAsync(dq, qs.data(), nq * sizeof(EvalQuery), hipMemcpyHostToDevice, c->stream);
+  hipLaunchKernelGGL(k_poly_eval_batch, dim3((unsigned)nq), dim3(OPN_T), 0, c->stream,
+                     (const EvalQuery*)dq, dout);
+  hipMemcpyAsync(evs_host, dout, nq * sizeof(Fp), hipMemcpyDeviceToHost, c->stream);
+  return 0;
+}
+
+// d_out[i] = Horner over polys[..][i] in ch (first poly highest power)
+static int dev_horner_comb(Ctx* c, ProverDev& pd, const std::vector<const Fp*>& polys,
+                           const Fp& ch, Fp* d_out, long n) {
+  if (polys.empty()) return TG_ERR_BADARG;
+  const Fp** dp = (const Fp**)pdev_stage(c, pd, polys.size() * sizeof(Fp*));
+  if (!dp) return TG_ERR_NOMEM;
+  hipMemcpyAsync(dp, polys.data(), polys.size() * sizeof(Fp*), hipMemcpyHostToDevice,
+                 c->stream);
+  hipLaunchKernelGGL(k_horner_comb, dim3(ntt_grid(n)), dim3(256), 0, c->stream,
+                     (const Fp* const*)dp, (int)polys.size(), ch, d_out, n);
+  return 0;
+}
+
+// independent divisions by (X - pt), one block each
+static int dev_kate_div(Ctx* c, ProverDev& pd, const std::vector<KateJob>& jobs) {
+  if (jobs.empty()) return 0;
+  KateJob* dj = (KateJob*)pdev_stage(c, pd, jobs.size() * sizeof(KateJob));
+  if (!dj) return TG_ERR_NOMEM;
+  hipMemcpyAsync(dj, jobs.data(), jobs.size() * sizeof(KateJob), hipMemcpyHostToDevice,
+                 c->stream);
+  hipLaunchKernelGGL(k_kate_div, dim3((unsigned)jobs.size()), dim3(OPN_T), 0, c->stream,
+                     (const KateJob*)dj);
+  return 0;
+}
+
+// The IPA rounds over the first 2^k bases of d_g, on device vectors d_pp
+// (the polynomial), d_bvec (powers of the opening point) and d_wfold (ones
+// on entry), all 2^k long and folded in place. L_j / R_j are MSMs over the
+// ORIGINAL bases with folded scalar vectors (wfold tracks the g-fold
+// coefficients) instead of folding the point vector itself — the group
+// elements are identical. Per round the host only draws the two blinds
+// (draw), adds the U / W terms, and hands L, R to emit, which returns the
+// round challenge. Returns pp[0] in a_out; blind_acc is updated in place.
+// lap(0) / lap(1) close a host / MSM span for the caller's stage timing.
+template <class DrawFn, class EmitFn, class LapFn>
+static int ipa_rounds_dev(Ctx* c, ProverDev& pd, int k, Fp* d_pp, Fp* d_bvec, Fp* d_wfold,
+                          const FixedMulTab& utab, const FixedMulTab& wtab, Fp& blind_acc,
+                          Fp& a_out, DrawFn&& draw, EmitFn&& emit, LapFn&& lap) {
+  long n = 1L << k;
+  int rc = gpu_msm_reserve(c, n, 2);
+  if (rc) return rc;
+  Fp* d_part = pdev_small(c, pd, 2 * OPN_GRID_MAX);
+  if (!d_part) return TG_ERR_NOMEM;
+  int grid = opn_grid(n);
+  std::vector<Fp> part(2 * (size_t)grid);
+  long half = n >> 1;
+  for (int round = 0; round < k; round++, half >>= 1) {
+    Fp l_rand, r_rand;
+    draw(l_rand, r_rand);
+    hipLaunchKernelGGL(k_ipa_prepare, dim3(grid), dim3(256), 0, c->stream,
+                       (const Fp*)d_pp, (const Fp*)d_bvec, (const Fp*)d_wfold, n, half,
+                       (Fp*)c->d_scalars, d_part);
+    hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(Fp), hipMemcpyDeviceToHost,
+                   c->stream);
+    lap(0);
+    VestaAff LR[2];
+    Fp zeros[2] = {fd_zero<FpCfg>(), fd_zero<FpCfg>()};
+    if ((rc = gpu_msm_commit_canon(c, n, 2, c->d_g, zeros, LR, &wtab))) return rc;
+    lap(1);
+    Fp value_l = fd_zero<FpCfg>(), value_r = fd_zero<FpCfg>();
+    for (int b = 0; b < grid; b++) {
+      value_l = fd_add(value_l, part[2 * b]);
+      value_r = fd_add(value_r, part[2 * b + 1]);
+    }
+    VestaJac Lj = jac_from_aff(LR[0]), Rj = jac_from_aff(LR[1]);
+    Lj = jac_add(Lj, utab.mul(value_l));
+    Lj = jac_add(Lj, wtab.mul(l_rand));
+    Rj = jac_add(Rj, utab.mul(value_r));
+    Rj = jac_add(Rj, wtab.mul(r_rand));
+    Fp uch;
+    if ((rc = emit(jac_to_aff(Lj), jac_to_aff(Rj), uch))) return rc;
+    Fp uch_inv = fd_inv(uch);
+    long topbit = (long)1 << (k - 1 - round);
+    hipLaunchKernelGGL(k_ipa_fold, dim3(grid), dim3(256), 0, c->stream, d_pp, d_bvec,
+                       d_wfold, n, half, topbit, uch, uch_inv);
+    blind_acc = fd_add(blind_acc, fd_mul(uch, l_rand));
+    blind_acc = fd_add(blind_acc, fd_mul(uch_inv, r_rand));
+    lap(0);
+  }
+  hipMemcpyAsync(&a_out, d_pp, sizeof(Fp), hipMemcpyDeviceToHost, c->stream);
+  return hipStreamSynchronize(c->stream) == hipSuccess ? 0 : TG_ERR_HIP;
 }
 
 // single-MSM wrapper (keygen-time calls before the W table exists pass
@@ -395,14 +562,17 @@ __global__ void __launch_bounds__(256, 1) k_h_fold(const HFoldArgs* __restrict__
 struct PPk {
   PDesc d;
   Fp omega, omega_inv, zeta, zeta_inv, delta, n_inv, ext_n_inv;
-  std::vector<std::vector<Fp>> fixed_coeff, fixed_ext;
-  std::vector<std::vector<Fp>> sigma_lag, sigma_coeff, sigma_ext;
+  std::vector<std::vector<Fp>> fixed_ext;
+  std::vector<std::vector<Fp>> sigma_lag, sigma_ext;
   std::vector<Fp> l0_ext, llast_ext, lactive_ext, t_inv_ext, x_ext;
   Fp vk_repr;
   std::vector<VestaAff> sigma_commits, fixed_commits;
   FixedMulTab wtab, utab;  // fast [s]W / [s]U (blinds, IPA inner-product terms)
   // device-resident h-fold inputs (uploaded once at keygen)
   std::vector<Fp*> d_fixed_ext, d_sigma_ext;
+  // coefficient form of the fixed and sigma polynomials (n each), read by
+  // the opening phase on the device
+  std::vector<Fp*> d_fixed_coeff, d_sigma_coeff;
   Fp *d_l0 = nullptr, *d_llast = nullptr, *d_lactive = nullptr, *d_tinv = nullptr,
      *d_xext = nullptr;
   ExprOp* d_ops = nullptr;
@@ -486,20 +656,28 @@ static int ppk_keygen(Ctx* c, PPk& pk, const uint8_t* desc, size_t desc_len) {
       cur = fd_mul(cur, mu);
     }
   }
+  // coefficient form -> the key's device copy (gpu_lag_to_coeff leaves it
+  // in ws0 as well as on the host)
+  auto keep_coeff = [&](Fp*& dst) -> int {
+    if (hipMalloc(&dst, n * sizeof(Fp)) != hipSuccess) return TG_ERR_NOMEM;
+    hipMemcpyAsync(dst, pk.pd.ws0, n * sizeof(Fp), hipMemcpyDeviceToDevice, c->stream);
+    return 0;
+  };
   // fixed transforms (GPU)
-  pk.fixed_coeff.resize(d.n_fixed);
   pk.fixed_ext.resize(d.n_fixed);
+  pk.d_fixed_coeff.assign(d.n_fixed, nullptr);
   for (int col = 0; col < d.n_fixed; col++) {
-    pk.fixed_coeff[col] = d.fixed_lag[col];
-    if (gpu_lag_to_coeff(c, pk.pd, pk.fixed_coeff[col].data(), d.k, pk.n_inv)) return TG_ERR_HIP;
+    std::vector<Fp> coeff = d.fixed_lag[col];
+    if (gpu_lag_to_coeff(c, pk.pd, coeff.data(), d.k, pk.n_inv)) return TG_ERR_HIP;
+    if (keep_coeff(pk.d_fixed_coeff[col])) return TG_ERR_NOMEM;
     pk.fixed_ext[col].resize(ext_n);
-    if (gpu_coeff_to_ext(c, pk.pd, pk.fixed_coeff[col].data(), pk.fixed_ext[col].data(),
-                         d.k, d.ext_k, pk.zeta))
+    if (gpu_coeff_to_ext(c, pk.pd, coeff.data(), pk.fixed_ext[col].data(), d.k, d.ext_k,
+                         pk.zeta))
       return TG_ERR_HIP;
   }
   // sigma polys
   pk.sigma_lag.resize(d.n_perm);
-  pk.sigma_coeff.resize(d.n_perm);
+  pk.d_sigma_coeff.assign(d.n_perm, nullptr);
   pk.sigma_ext.resize(d.n_perm);
   {
     std::vector<Fp> dpow(d.n_perm), wpow(n);
@@ -516,11 +694,12 @@ static int ppk_keygen(Ctx* c, PPk& pk, const uint8_t* desc, size_t desc_len) {
         auto [cj, ri] = d.sigma_map[(size_t)j * n + i];
         pk.sigma_lag[j][i] = fd_mul(dpow[cj], wpow[ri]);
       }
-      pk.sigma_coeff[j] = pk.sigma_lag[j];
-      if (gpu_lag_to_coeff(c, pk.pd, pk.sigma_coeff[j].data(), d.k, pk.n_inv)) return TG_ERR_HIP;
+      std::vector<Fp> coeff = pk.sigma_lag[j];
+      if (gpu_lag_to_coeff(c, pk.pd, coeff.data(), d.k, pk.n_inv)) return TG_ERR_HIP;
+      if (keep_coeff(pk.d_sigma_coeff[j])) return TG_ERR_NOMEM;
       pk.sigma_ext[j].resize(ext_n);
-      if (gpu_coeff_to_ext(c, pk.pd, pk.sigma_coeff[j].data(), pk.sigma_ext[j].data(),
-                           d.k, d.ext_k, pk.zeta))
+      if (gpu_coeff_to_ext(c, pk.pd, coeff.data(), pk.sigma_ext[j].data(), d.k, d.ext_k,
+                           pk.zeta))
         return TG_ERR_HIP;
     }
   }
@@ -716,6 +895,14 @@ static int ppk_keygen(Ctx* c, PPk& pk, const uint8_t* desc, size_t desc_len) {
                    hipMemcpyHostToDevice, c->stream);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return TG_ERR_HIP;
   }
+  // the per-proof coefficient pool, sized from the descriptor: instance,
+  // advice, permutation z chunks, lookup z / A' / S', then the random
+  // polynomial, the collapsed h and the IPA's s polynomial
+  {
+    int nchunks = (d.n_perm + d.chunk_len - 1) / d.chunk_len;
+    int slots = 1 + d.n_advice + nchunks + 3 * d.n_lookups + 3;
+    if (!pdev_slots(c, pk.pd.coef, pk.pd.coef_slots, slots, n)) return TG_ERR_NOMEM;
+  }
   pk.ready = true;
   return 0;
 }
@@ -909,15 +1096,21 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
     return TG_ERR_HIP;
   ts.common_point(inst_cm);
   st_.mark("instance_commit");
-  std::vector<Fp> inst_coeff = inst_lag;
-  if (gpu_lag_to_coeff(c, pd, inst_coeff.data(), d.k, pk.n_inv)) return TG_ERR_HIP;
   // device ext-buffer layout: advice | inst | permz | lkz | lkAp | lkSp | h
   const int EB_ADV = 0, EB_INST = EB_ADV + d.n_advice, EB_PZ = EB_INST + d.n_instance;
   const int EB_LZ = EB_PZ + nchunks, EB_AP = EB_LZ + nlk, EB_SP = EB_AP + nlk;
   const int EB_H = EB_SP + nlk;
+  // coefficient pool slots (sized at keygen): the coefficient form stays on
+  // the device, where the opening phase reads it
+  const int CS_INST = 0, CS_ADV = 1, CS_PZ = CS_ADV + d.n_advice, CS_LZ = CS_PZ + nchunks;
+  const int CS_AP = CS_LZ + nlk, CS_SP = CS_AP + nlk, CS_RAND = CS_SP + nlk;
+  const int CS_H = CS_RAND + 1, CS_S = CS_H + 1;
+  if (pd.coef_slots < CS_S + 1) return TG_ERR_STATE;
+  auto cslot = [&](int idx) { return pd.coef + (size_t)idx * n; };
   Fp* d_inst_ext = pdev_ext_buf(pd, EB_INST);
   if (!d_inst_ext) return TG_ERR_NOMEM;
-  if (gpu_coeff_to_ext_dev(c, pd, inst_coeff.data(), d_inst_ext, d.k, d.ext_k, pk.zeta))
+  if (gpu_lag_to_coeff_ext_dev(c, pd, inst_lag.data(), cslot(CS_INST), d_inst_ext, d.k,
+                               d.ext_k, pk.n_inv, pk.zeta))
     return TG_ERR_HIP;
 
   // 2. advice
@@ -937,13 +1130,11 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
     for (int col = 0; col < d.n_advice; col++)
       if (ts.write_point(cms[col])) return TG_ERR_BADARG;
   }
-  std::vector<std::vector<Fp>> advice_coeff(d.n_advice);
   for (int col = 0; col < d.n_advice; col++) {
-    advice_coeff[col] = advice_lag[col];
     Fp* dbuf = pdev_ext_buf(pd, EB_ADV + col);
     if (!dbuf) return TG_ERR_NOMEM;
-    if (gpu_lag_to_coeff_ext_dev(c, pd, advice_coeff[col].data(), dbuf, d.k, d.ext_k,
-                                 pk.n_inv, pk.zeta))
+    if (gpu_lag_to_coeff_ext_dev(c, pd, advice_lag[col].data(), cslot(CS_ADV + col), dbuf,
+                                 d.k, d.ext_k, pk.n_inv, pk.zeta))
       return TG_ERR_HIP;
   }
 
@@ -952,8 +1143,6 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
 
   // 3. lookups
   std::vector<std::vector<Fp>> lkA(nlk), lkS(nlk), lkAp(nlk), lkSp(nlk);
-  std::vector<std::vector<Fp>> lkAp_coeff(nlk), lkSp_coeff(nlk), lkAp_ext(nlk),
-      lkSp_ext(nlk);
   std::vector<Fp> lkAp_blind(nlk), lkSp_blind(nlk);
   {
     PEvalCtx ec{&d, d.fixed_lag.data(), advice_lag.data(), &inst_lag, n, 1};
@@ -1121,8 +1310,12 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   drbg_fields_par(rng, random_poly.data(), n);
   Fp random_blind = rng.field<FpCfg>();
   {
+    // uploaded once into its pool slot: the commit and the openings read it there
     VestaAff cm;
-    if (gpu_msm_commit(c, pd, random_poly.data(), n, c->d_g, random_blind, c->h_w, cm, &pk.wtab))
+    hipMemcpyAsync(cslot(CS_RAND), random_poly.data(), n * sizeof(Fp),
+                   hipMemcpyHostToDevice, c->stream);
+    if (gpu_msm_commit_batch_dev(c, cslot(CS_RAND), n, 1, c->d_g, &random_blind, &cm,
+                                 &pk.wtab))
       return TG_ERR_HIP;
     if (ts.write_point(cm)) return TG_ERR_BADARG;
   }
@@ -1131,30 +1324,25 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   Fp ych = ts.squeeze();
 
   // 7. h on extended coset (transforms via GPU; fold on host OpenMP)
-  std::vector<std::vector<Fp>> permz_coeff(nchunks);
   for (int ch = 0; ch < nchunks; ch++) {
-    permz_coeff[ch] = permz_lag[ch];
     Fp* dbuf = pdev_ext_buf(pd, EB_PZ + ch);
     if (!dbuf) return TG_ERR_NOMEM;
-    if (gpu_lag_to_coeff_ext_dev(c, pd, permz_coeff[ch].data(), dbuf, d.k, d.ext_k,
-                                 pk.n_inv, pk.zeta))
+    if (gpu_lag_to_coeff_ext_dev(c, pd, permz_lag[ch].data(), cslot(CS_PZ + ch), dbuf, d.k,
+                                 d.ext_k, pk.n_inv, pk.zeta))
       return TG_ERR_HIP;
   }
-  std::vector<std::vector<Fp>> lkz_coeff(nlk);
   for (int l = 0; l < nlk; l++) {
-    lkz_coeff[l] = lkz_lag[l];
-    if (gpu_lag_to_coeff_ext_dev(c, pd, lkz_coeff[l].data(), pdev_ext_buf(pd, EB_LZ + l),
-                                 d.k, d.ext_k, pk.n_inv, pk.zeta))
+    Fp *dz = pdev_ext_buf(pd, EB_LZ + l), *dap = pdev_ext_buf(pd, EB_AP + l),
+       *dsp = pdev_ext_buf(pd, EB_SP + l);
+    if (!dz || !dap || !dsp) return TG_ERR_NOMEM;
+    if (gpu_lag_to_coeff_ext_dev(c, pd, lkz_lag[l].data(), cslot(CS_LZ + l), dz, d.k,
+                                 d.ext_k, pk.n_inv, pk.zeta))
       return TG_ERR_HIP;
-    lkAp_coeff[l] = lkAp[l];
-    if (gpu_lag_to_coeff_ext_dev(c, pd, lkAp_coeff[l].data(),
-                                 pdev_ext_buf(pd, EB_AP + l), d.k, d.ext_k, pk.n_inv,
-                                 pk.zeta))
+    if (gpu_lag_to_coeff_ext_dev(c, pd, lkAp[l].data(), cslot(CS_AP + l), dap, d.k, d.ext_k,
+                                 pk.n_inv, pk.zeta))
       return TG_ERR_HIP;
-    lkSp_coeff[l] = lkSp[l];
-    if (gpu_lag_to_coeff_ext_dev(c, pd, lkSp_coeff[l].data(),
-                                 pdev_ext_buf(pd, EB_SP + l), d.k, d.ext_k, pk.n_inv,
-                                 pk.zeta))
+    if (gpu_lag_to_coeff_ext_dev(c, pd, lkSp[l].data(), cslot(CS_SP + l), dsp, d.k, d.ext_k,
+                                 pk.n_inv, pk.zeta))
       return TG_ERR_HIP;
   }
   st_.mark("z_transforms");
@@ -1243,25 +1431,20 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
                        (const HFoldArgs*)pd.d_hargs);
     st_.mark("h_fold_rest");
   }
-  std::vector<Fp> h_coeff(ext_n);
-  {
-    // iNTT + zeta-undistribute directly on the device h buffer
-    Fp* dH = pdev_ext_buf(pd, EB_H);
-    if (ntt_run(dH, pd.ws1, pd.plan_ext, d.ext_k, true, c->stream, &pk.ext_n_inv,
-                ntt_noprof) != hipSuccess)
-      return TG_ERR_HIP;
-    coset_scale_launch(dH, (u64)ext_n, pk.zeta_inv, c->stream);
-    hipMemcpyAsync(h_coeff.data(), dH, ext_n * sizeof(Fp), hipMemcpyDeviceToHost,
-                   c->stream);
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return TG_ERR_HIP;
-  }
+  // iNTT + zeta-undistribute directly on the device h buffer; the pieces
+  // of h's coefficient form stay there (commit scalars, then the collapse)
+  Fp* dH = pdev_ext_buf(pd, EB_H);
+  if (ntt_run(dH, pd.ws1, pd.plan_ext, d.ext_k, true, c->stream, &pk.ext_n_inv,
+              ntt_noprof) != hipSuccess)
+    return TG_ERR_HIP;
+  coset_scale_launch(dH, (u64)ext_n, pk.zeta_inv, c->stream);
   int npieces = (int)(ext_n / n);
   std::vector<Fp> h_blind(npieces);
   for (int pce = 0; pce < npieces; pce++) h_blind[pce] = rng.field<FpCfg>();
   {
     std::vector<VestaAff> cms(npieces);
-    if (gpu_msm_commit_batch(c, pd, h_coeff.data(), n, npieces, c->d_g, h_blind.data(),
-                             cms.data(), &pk.wtab))
+    if (gpu_msm_commit_batch_dev(c, dH, n, npieces, c->d_g, h_blind.data(), cms.data(),
+                                 &pk.wtab))
       return TG_ERR_HIP;
     for (int pce = 0; pce < npieces; pce++)
       if (ts.write_point(cms[pce])) return TG_ERR_BADARG;
@@ -1272,74 +1455,71 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   Fp xn = x;
   for (int i = 0; i < d.k; i++) xn = fd_sqr(xn);
 
-  // 8. evals
+  // 8. evals, on the device. Every point is known once x is squeezed and no
+  // challenge is drawn between the evaluation writes, so all of step 8 is
+  // one batched launch, one download and one synchronisation; the scalars
+  // then go to the transcript in the order the queries were listed.
   auto rot_pt = [&](const Fp& xx, int rot) {
     Fp w = fd_one_mont<FpCfg>();
     const Fp& base = rot < 0 ? pk.omega_inv : pk.omega;
     for (int i = 0; i < (rot < 0 ? -rot : rot); i++) w = fd_mul(w, base);
     return fd_mul(xx, w);
   };
-  std::vector<Fp> adv_eval(d.n_advice_q), fix_eval(d.n_fixed_q), sig_eval(d.n_perm);
-  Fp rand_eval;
-  Fp pz_eval[8][2], pz_last_eval[8], lk_eval[4][5];
-  for (int q = 0; q < d.n_advice_q; q++) {
-    adv_eval[q] =
-        ppoly_eval(advice_coeff[d.advice_q[q].col].data(), n, rot_pt(x, d.advice_q[q].rot));
-    ts.write_scalar(adv_eval[q]);
-  }
-  for (int q = 0; q < d.n_fixed_q; q++) {
-    fix_eval[q] =
-        ppoly_eval(pk.fixed_coeff[d.fixed_q[q].col].data(), n, rot_pt(x, d.fixed_q[q].rot));
-    ts.write_scalar(fix_eval[q]);
-  }
-  rand_eval = ppoly_eval(random_poly.data(), n, x);
-  ts.write_scalar(rand_eval);
-  for (int j = 0; j < d.n_perm; j++) {
-    sig_eval[j] = ppoly_eval(pk.sigma_coeff[j].data(), n, x);
-    ts.write_scalar(sig_eval[j]);
-  }
-  Fp x_next = rot_pt(x, 1), x_prev = rot_pt(x, -1), x_last = rot_pt(x, -(d.bf + 1));
-  for (int ch = 0; ch < nchunks; ch++) {
-    pz_eval[ch][0] = ppoly_eval(permz_coeff[ch].data(), n, x);
-    ts.write_scalar(pz_eval[ch][0]);
-    pz_eval[ch][1] = ppoly_eval(permz_coeff[ch].data(), n, x_next);
-    ts.write_scalar(pz_eval[ch][1]);
-  }
-  for (int ch = 0; ch < nchunks - 1; ch++) {
-    pz_last_eval[ch] = ppoly_eval(permz_coeff[ch].data(), n, x_last);
-    ts.write_scalar(pz_last_eval[ch]);
-  }
-  for (int l = 0; l < nlk; l++) {
-    lk_eval[l][0] = ppoly_eval(lkz_coeff[l].data(), n, x);
-    ts.write_scalar(lk_eval[l][0]);
-    lk_eval[l][1] = ppoly_eval(lkz_coeff[l].data(), n, x_next);
-    ts.write_scalar(lk_eval[l][1]);
-    lk_eval[l][2] = ppoly_eval(lkAp_coeff[l].data(), n, x);
-    ts.write_scalar(lk_eval[l][2]);
-    lk_eval[l][3] = ppoly_eval(lkAp_coeff[l].data(), n, x_prev);
-    ts.write_scalar(lk_eval[l][3]);
-    lk_eval[l][4] = ppoly_eval(lkSp_coeff[l].data(), n, x);
-    ts.write_scalar(lk_eval[l][4]);
-  }
-  // h collapsed
-  std::vector<Fp> h_collapsed(h_coeff.begin() + (size_t)(npieces - 1) * n,
-                              h_coeff.begin() + (size_t)npieces * n);
+  // h collapsed: Horner over the pieces in x^n, highest piece first
   Fp h_collapsed_blind = h_blind[npieces - 1];
-  for (int pce = npieces - 2; pce >= 0; pce--) {
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-    for (long i = 0; i < n; i++)
-      h_collapsed[i] = fd_add(fd_mul(h_collapsed[i], xn), h_coeff[(size_t)pce * n + i]);
+  for (int pce = npieces - 2; pce >= 0; pce--)
     h_collapsed_blind = fd_add(fd_mul(h_collapsed_blind, xn), h_blind[pce]);
+  {
+    std::vector<const Fp*> pieces;
+    for (int pce = npieces - 1; pce >= 0; pce--) pieces.push_back(dH + (size_t)pce * n);
+    if (dev_horner_comb(c, pd, pieces, xn, cslot(CS_H), n)) return TG_ERR_HIP;
   }
-  Fp h_eval = ppoly_eval(h_collapsed.data(), n, x);
+  std::vector<Fp> adv_eval(d.n_advice_q), fix_eval(d.n_fixed_q), sig_eval(d.n_perm);
+  Fp rand_eval, h_eval;
+  Fp pz_eval[8][2], pz_last_eval[8], lk_eval[4][5];
   std::vector<Fp> inst_eval(d.n_instance_q);
-  for (int q = 0; q < d.n_instance_q; q++)
-    inst_eval[q] = ppoly_eval(inst_coeff.data(), n, rot_pt(x, d.instance_q[q].rot));
+  Fp x_next = rot_pt(x, 1), x_prev = rot_pt(x, -1), x_last = rot_pt(x, -(d.bf + 1));
+  {
+    std::vector<EvalQuery> evq;
+    std::vector<Fp*> dest;  // where each query's value goes
+    auto ask = [&](const Fp* poly, const Fp& pt, Fp& into) {
+      evq.push_back(EvalQuery{poly, n, pt});
+      dest.push_back(&into);
+    };
+    for (int q = 0; q < d.n_advice_q; q++)
+      ask(cslot(CS_ADV + d.advice_q[q].col), rot_pt(x, d.advice_q[q].rot), adv_eval[q]);
+    for (int q = 0; q < d.n_fixed_q; q++)
+      ask(pk.d_fixed_coeff[d.fixed_q[q].col], rot_pt(x, d.fixed_q[q].rot), fix_eval[q]);
+    ask(cslot(CS_RAND), x, rand_eval);
+    for (int j = 0; j < d.n_perm; j++) ask(pk.d_sigma_coeff[j], x, sig_eval[j]);
+    for (int ch = 0; ch < nchunks; ch++) {
+      ask(cslot(CS_PZ + ch), x, pz_eval[ch][0]);
+      ask(cslot(CS_PZ + ch), x_next, pz_eval[ch][1]);
+    }
+    for (int ch = 0; ch < nchunks - 1; ch++) ask(cslot(CS_PZ + ch), x_last, pz_last_eval[ch]);
+    for (int l = 0; l < nlk; l++) {
+      ask(cslot(CS_LZ + l), x, lk_eval[l][0]);
+      ask(cslot(CS_LZ + l), x_next, lk_eval[l][1]);
+      ask(cslot(CS_AP + l), x, lk_eval[l][2]);
+      ask(cslot(CS_AP + l), x_prev, lk_eval[l][3]);
+      ask(cslot(CS_SP + l), x, lk_eval[l][4]);
+    }
+    size_t n_written = evq.size();  // the rest is not written to the transcript
+    ask(cslot(CS_H), x, h_eval);
+    for (int q = 0; q < d.n_instance_q; q++)
+      ask(cslot(CS_INST), rot_pt(x, d.instance_q[q].rot), inst_eval[q]);
+    std::vector<Fp> evs(evq.size());
+    if (dev_poly_eval_batch(c, pd, evq, evs.data())) return TG_ERR_HIP;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return TG_ERR_HIP;
+    for (size_t i = 0; i < evs.size(); i++) {
+      *dest[i] = evs[i];
+      if (i < n_written) ts.write_scalar(evs[i]);
+    }
+  }
 
   st_.mark("evals");
-  // 9. multiopen query list (order mirrors the oracle exactly)
+  // 9. multiopen query list (order mirrors the oracle exactly); the
+  // polynomials are device coefficient vectors
   struct PolyRef {
     const Fp* coeff;
     Fp blind;
@@ -1353,26 +1533,26 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   auto add_q = [&](int pid, const Fp& pt, const Fp& ev) {
     queries.push_back({pid, pt, ev});
   };
-  int pid_inst = add_poly(inst_coeff.data(), one);
+  int pid_inst = add_poly(cslot(CS_INST), one);
   std::vector<int> pid_adv(d.n_advice);
   for (int col = 0; col < d.n_advice; col++)
-    pid_adv[col] = add_poly(advice_coeff[col].data(), advice_blind[col]);
+    pid_adv[col] = add_poly(cslot(CS_ADV + col), advice_blind[col]);
   std::vector<int> pid_pz(nchunks);
   for (int ch = 0; ch < nchunks; ch++)
-    pid_pz[ch] = add_poly(permz_coeff[ch].data(), permz_blind[ch]);
+    pid_pz[ch] = add_poly(cslot(CS_PZ + ch), permz_blind[ch]);
   std::vector<int> pid_lz(nlk), pid_lap(nlk), pid_lsp(nlk);
   for (int l = 0; l < nlk; l++) {
-    pid_lz[l] = add_poly(lkz_coeff[l].data(), lkz_blind[l]);
-    pid_lap[l] = add_poly(lkAp_coeff[l].data(), lkAp_blind[l]);
-    pid_lsp[l] = add_poly(lkSp_coeff[l].data(), lkSp_blind[l]);
+    pid_lz[l] = add_poly(cslot(CS_LZ + l), lkz_blind[l]);
+    pid_lap[l] = add_poly(cslot(CS_AP + l), lkAp_blind[l]);
+    pid_lsp[l] = add_poly(cslot(CS_SP + l), lkSp_blind[l]);
   }
   std::vector<int> pid_fix(d.n_fixed);
   for (int col = 0; col < d.n_fixed; col++)
-    pid_fix[col] = add_poly(pk.fixed_coeff[col].data(), one);
+    pid_fix[col] = add_poly(pk.d_fixed_coeff[col], one);
   std::vector<int> pid_sig(d.n_perm);
-  for (int j = 0; j < d.n_perm; j++) pid_sig[j] = add_poly(pk.sigma_coeff[j].data(), one);
-  int pid_h = add_poly(h_collapsed.data(), h_collapsed_blind);
-  int pid_rand = add_poly(random_poly.data(), random_blind);
+  for (int j = 0; j < d.n_perm; j++) pid_sig[j] = add_poly(pk.d_sigma_coeff[j], one);
+  int pid_h = add_poly(cslot(CS_H), h_collapsed_blind);
+  int pid_rand = add_poly(cslot(CS_RAND), random_blind);
 
   for (int q = 0; q < d.n_instance_q; q++)
     add_q(pid_inst, rot_pt(x, d.instance_q[q].rot), inst_eval[q]);
@@ -1425,169 +1605,139 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
     poly_set[pid] = found;
   }
   int n_sets = (int)set_pts.size();
-  std::vector<std::vector<Fp>> q_poly(n_sets, std::vector<Fp>(n, fd_zero<FpCfg>()));
+  // device work vectors: q_poly[s], each set's quotient, bvec, wfold
+  if (!pdev_slots(c, pd.open_ws, pd.open_slots, 2 * n_sets + 2, n)) return TG_ERR_NOMEM;
+  auto wslot = [&](int idx) { return pd.open_ws + (size_t)idx * n; };
+  auto q_poly = [&](int s) { return wslot(s); };
+  auto quot = [&](int s) { return wslot(n_sets + s); };
+  Fp *d_bvec = wslot(2 * n_sets), *d_wfold = wslot(2 * n_sets + 1);
+  // q_poly[s] = Horner in x1 over the set's polynomials, in query order;
+  // the blinds and evaluations combine on the host (scalars)
+  std::vector<std::vector<const Fp*>> set_polys(n_sets);
   std::vector<Fp> q_blind(n_sets, fd_zero<FpCfg>());
   std::vector<std::vector<Fp>> q_ev(n_sets);
   for (int s = 0; s < n_sets; s++) q_ev[s].assign(set_pts[s].size(), fd_zero<FpCfg>());
   for (int pid : order) {
     int s = poly_set[pid];
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-    for (long i = 0; i < n; i++)
-      q_poly[s][i] = fd_add(fd_mul(q_poly[s][i], x1), polys[pid].coeff[i]);
+    set_polys[s].push_back(polys[pid].coeff);
     q_blind[s] = fd_add(fd_mul(q_blind[s], x1), polys[pid].blind);
     for (size_t j = 0; j < q_ev[s].size(); j++)
       q_ev[s][j] = fd_add(fd_mul(q_ev[s][j], x1), pevs[pid][j]);
   }
-  std::vector<Fp> f_poly(n, fd_zero<FpCfg>()), tmp(n);
-  for (int s = 0; s < n_sets; s++) {
-    tmp = q_poly[s];
-    long cur = n;
-    for (const Fp& pt : set_pts[s]) {
-      pkate_division(tmp.data(), tmp.data(), cur, pt);
-      cur--;
-      tmp[cur] = fd_zero<FpCfg>();
+  for (int s = 0; s < n_sets; s++)
+    if (dev_horner_comb(c, pd, set_polys[s], x1, q_poly(s), n)) return TG_ERR_HIP;
+  // quotient of each set by its points, one after the other (the length
+  // drops by one per point); the sets divide side by side
+  {
+    size_t max_pts = 0;
+    for (int s = 0; s < n_sets; s++) max_pts = std::max(max_pts, set_pts[s].size());
+    for (size_t j = 0; j < max_pts; j++) {
+      std::vector<KateJob> jobs;
+      for (int s = 0; s < n_sets; s++)
+        if (set_pts[s].size() > j)
+          jobs.push_back(KateJob{j == 0 ? q_poly(s) : quot(s), quot(s), n - (long)j,
+                                 set_pts[s][j]});
+      if (dev_kate_div(c, pd, jobs)) return TG_ERR_HIP;
     }
-    if (s == 0) {
-      f_poly = tmp;
-    } else {
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-      for (long i = 0; i < n; i++) f_poly[i] = fd_add(fd_mul(f_poly[i], x2), tmp[i]);
-    }
+  }
+  // f = Horner in x2 over the quotients (in place over the first)
+  Fp* d_f = quot(0);
+  {
+    std::vector<const Fp*> qs;
+    for (int s = 0; s < n_sets; s++) qs.push_back(quot(s));
+    if (dev_horner_comb(c, pd, qs, x2, d_f, n)) return TG_ERR_HIP;
   }
   Fp f_blind = rng.field<FpCfg>();
   {
     VestaAff cm;
-    if (gpu_msm_commit(c, pd, f_poly.data(), n, c->d_g, f_blind, c->h_w, cm, &pk.wtab))
+    if (gpu_msm_commit_batch_dev(c, d_f, n, 1, c->d_g, &f_blind, &cm, &pk.wtab))
       return TG_ERR_HIP;
     if (ts.write_point(cm)) return TG_ERR_BADARG;
   }
   st_.mark("multiopen_f");
   Fp x3 = ts.squeeze();
-  std::vector<Fp> q_at_x3(n_sets);
-  for (int s = 0; s < n_sets; s++) {
-    q_at_x3[s] = ppoly_eval(q_poly[s].data(), n, x3);
-    ts.write_scalar(q_at_x3[s]);
+  // the IPA's s polynomial is drawn here (the next draws of the rng stream;
+  // the transcript is not involved), so that its evaluation at x3 shares
+  // the launch with the q_poly evaluations
+  std::vector<Fp> s_poly(n);
+  drbg_fields_par(rng, s_poly.data(), n);
+  hipMemcpyAsync(cslot(CS_S), s_poly.data(), n * sizeof(Fp), hipMemcpyHostToDevice,
+                 c->stream);
+  std::vector<Fp> q_at_x3(n_sets + 1);
+  {
+    std::vector<EvalQuery> evq;
+    for (int s = 0; s < n_sets; s++) evq.push_back(EvalQuery{q_poly(s), n, x3});
+    evq.push_back(EvalQuery{cslot(CS_S), n, x3});
+    if (dev_poly_eval_batch(c, pd, evq, q_at_x3.data())) return TG_ERR_HIP;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return TG_ERR_HIP;
   }
+  for (int s = 0; s < n_sets; s++) ts.write_scalar(q_at_x3[s]);
   Fp x4 = ts.squeeze();
-  std::vector<Fp>& final_poly = f_poly;
+  // final = Horner in x4 over f, q_poly[0], q_poly[1], ... (in place over f)
   Fp final_blind = f_blind;
-  for (int s = 0; s < n_sets; s++) {
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-    for (long i = 0; i < n; i++)
-      final_poly[i] = fd_add(fd_mul(final_poly[i], x4), q_poly[s][i]);
-    final_blind = fd_add(fd_mul(final_blind, x4), q_blind[s]);
+  {
+    std::vector<const Fp*> qs{d_f};
+    for (int s = 0; s < n_sets; s++) {
+      qs.push_back(q_poly(s));
+      final_blind = fd_add(fd_mul(final_blind, x4), q_blind[s]);
+    }
+    if (dev_horner_comb(c, pd, qs, x4, d_f, n)) return TG_ERR_HIP;
   }
 
   st_.mark("multiopen_final");
   // ---- IPA ----
-  std::vector<Fp> s_poly(n);
-  drbg_fields_par(rng, s_poly.data(), n);
-  {
-    Fp ev = ppoly_eval(s_poly.data(), n, x3);
-    s_poly[0] = fd_sub(s_poly[0], ev);
-  }
+  // s(x3) = 0: the constant term takes the evaluation off
+  s_poly[0] = fd_sub(s_poly[0], q_at_x3[n_sets]);
+  hipMemcpyAsync(cslot(CS_S), s_poly.data(), sizeof(Fp), hipMemcpyHostToDevice, c->stream);
   Fp s_blind = rng.field<FpCfg>();
   {
     VestaAff cm;
-    if (gpu_msm_commit(c, pd, s_poly.data(), n, c->d_g, s_blind, c->h_w, cm, &pk.wtab))
+    if (gpu_msm_commit_batch_dev(c, cslot(CS_S), n, 1, c->d_g, &s_blind, &cm, &pk.wtab))
       return TG_ERR_HIP;
     if (ts.write_point(cm)) return TG_ERR_BADARG;
   }
   Fp xi = ts.squeeze();
-  std::vector<Fp> pp(n);
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-  for (long i = 0; i < n; i++) pp[i] = fd_add(final_poly[i], fd_mul(s_poly[i], xi));
+  // pp = final + xi * s (in place over final); bvec = powers of x3
+  Fp* d_pp = d_f;
+  {
+    std::vector<const Fp*> qs{cslot(CS_S), d_f};
+    if (dev_horner_comb(c, pd, qs, xi, d_pp, n)) return TG_ERR_HIP;
+  }
   Fp blind_acc = fd_add(final_blind, fd_mul(s_blind, xi));
-  std::vector<Fp> bvec(n);
-  bvec[0] = fd_one_mont<FpCfg>();
-  for (long i = 1; i < n; i++) bvec[i] = fd_mul(bvec[i - 1], x3);
-  // IPA rounds: L_j/R_j are computed as MSMs over the ORIGINAL resident
-  // SRS bases g with host-folded scalar vectors (w_t tracks the g-fold
-  // coefficients), instead of folding the point vector itself on device —
-  // the group elements are identical, so proof bytes are unchanged, and the
-  // expensive per-round jacobian fold/normalize kernels disappear.
+  fill_powers_launch(d_bvec, n, x3, c->stream);
+  hipLaunchKernelGGL(k_fill_const, dim3(opn_grid(n)), dim3(256), 0, c->stream, d_wfold, n,
+                     one);
   st_.mark("ipa_setup");
   double tm_msm = 0, tm_host = 0;
-  auto lap = [&](double& acc) {
+  auto lap = [&](int which) {
     if (st_.on) {
       hipStreamSynchronize(c->stream);
       double t = StageTimer::now();
-      acc += t - st_.last;
+      (which ? tm_msm : tm_host) += t - st_.last;
       st_.last = t;
     }
   };
-  std::vector<Fp> wfold(n, fd_one_mont<FpCfg>());
-  std::vector<Fp> slr(2 * (size_t)n);
-  Fp* sl = slr.data();
-  Fp* sr = slr.data() + n;
-  long half = n >> 1;
-  for (int round = 0; round < d.k; round++, half >>= 1) {
-    long cur = half * 2;
-    Fp value_l = pinner(pp.data() + half, bvec.data(), half);
-    Fp value_r = pinner(pp.data(), bvec.data() + half, half);
-    Fp l_rand = rng.field<FpCfg>();
-    Fp r_rand = rng.field<FpCfg>();
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-    for (long t = 0; t < n; t++) {
-      long ci = t & (cur - 1);
-      if (ci < half) {
-        sl[t] = fd_mul(wfold[t], pp[half + ci]);
-        sr[t] = fd_zero<FpCfg>();
-      } else {
-        sl[t] = fd_zero<FpCfg>();
-        sr[t] = fd_mul(wfold[t], pp[ci - half]);
-      }
-    }
-    lap(tm_host);
-    VestaAff LR[2];
-    Fp zeros[2] = {fd_zero<FpCfg>(), fd_zero<FpCfg>()};
-    if (gpu_msm_commit_batch(c, pd, slr.data(), n, 2, c->d_g, zeros, LR, &pk.wtab))
-      return TG_ERR_HIP;
-    VestaAff &Lm = LR[0], &Rm = LR[1];
-    lap(tm_msm);
-    VestaJac Lj = jac_from_aff(Lm), Rj = jac_from_aff(Rm);
-    Lj = jac_add(Lj, pk.utab.mul(value_l));
-    Lj = jac_add(Lj, pk.wtab.mul(l_rand));
-    Rj = jac_add(Rj, pk.utab.mul(value_r));
-    Rj = jac_add(Rj, pk.wtab.mul(r_rand));
-    VestaAff La = jac_to_aff(Lj), Ra = jac_to_aff(Rj);
-    if (ts.write_point(La)) return TG_ERR_BADARG;
-    if (ts.write_point(Ra)) return TG_ERR_BADARG;
-    Fp uch = ts.squeeze();
-    Fp uch_inv = fd_inv(uch);
-    long topbit = (long)1 << (d.k - 1 - round);
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-    for (long t = 0; t < n; t++) {
-      if (t & topbit) wfold[t] = fd_mul(wfold[t], uch_inv);
-    }
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-    for (long i = 0; i < half; i++) {
-      pp[i] = fd_add(pp[i], fd_mul(pp[half + i], uch));
-      bvec[i] = fd_add(bvec[i], fd_mul(bvec[half + i], uch_inv));
-    }
-    blind_acc = fd_add(blind_acc, fd_mul(uch, l_rand));
-    blind_acc = fd_add(blind_acc, fd_mul(uch_inv, r_rand));
-    lap(tm_host);
+  Fp a_final;
+  {
+    int rc = ipa_rounds_dev(
+        c, pd, d.k, d_pp, d_bvec, d_wfold, pk.utab, pk.wtab, blind_acc, a_final,
+        [&](Fp& l_rand, Fp& r_rand) {
+          l_rand = rng.field<FpCfg>();
+          r_rand = rng.field<FpCfg>();
+        },
+        [&](const VestaAff& La, const VestaAff& Ra, Fp& uch) {
+          if (ts.write_point(La)) return (int)TG_ERR_BADARG;
+          if (ts.write_point(Ra)) return (int)TG_ERR_BADARG;
+          uch = ts.squeeze();
+          return 0;
+        },
+        lap);
+    if (rc) return rc;
   }
-  if (hipStreamSynchronize(c->stream) != hipSuccess) return TG_ERR_HIP;
   if (st_.on)
     fprintf(stderr, "# ipa-split host=%.1f msm=%.1f ms\n", tm_host * 1e3, tm_msm * 1e3);
   st_.mark("ipa");
-  ts.write_scalar(pp[0]);
+  ts.write_scalar(a_final);
   ts.write_scalar(blind_acc);
   proof_out = std::move(ts.proof);
   return 0;

@@ -265,68 +265,6 @@ inline void pprefix_prod(Fp* z, const Fp* r, long u, const Fp& init) {
   z[u] = acc;
 }
 
-// kate division q = a / (X - b), remainder dropped: q[i] = sum_{j>i} a[j] b^{j-i-1}.
-// Blocked two-pass form of the serial recurrence prev = a[i] + b*prev
-// (exact same values; ~2n muls, blocks parallel).
-inline void pkate_division(Fp* q, const Fp* a, long n, const Fp& b) {
-  const int T = 16;
-  long chunk = (n + T - 1) / T;
-  // pass 1: per block [lo,hi): local suffix Horner L_t = sum_{j in [lo,hi)} a[j] b^{j-lo}
-  Fp L[T], bp[T];  // bp = b^(hi-lo)
-  std::vector<Fp> asnap(a, a + n);  // allow q to alias a
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-  for (int t = 0; t < T; t++) {
-    long lo = t * chunk, hi = std::min(lo + chunk, n);
-    Fp acc = fd_zero<FpCfg>();
-    for (long i = hi - 1; i >= lo; i--) acc = fd_add(fd_mul(acc, b), asnap[i]);
-    L[t] = acc;
-    bp[t] = fp_pow_small(b, hi > lo ? hi - lo : 0);
-  }
-  // serial: carry into each block from above: C_t = Horner of blocks > t
-  Fp C[T];
-  Fp acc = fd_zero<FpCfg>();
-  for (int t = T - 1; t >= 0; t--) {
-    C[t] = acc;
-    acc = fd_add(fd_mul(acc, bp[t]), L[t]);
-  }
-  // pass 2: per block, run the recurrence with the incoming carry
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-  for (int t = 0; t < T; t++) {
-    long lo = t * chunk, hi = std::min(lo + chunk, n);
-    Fp prev = C[t];  // value of q at index hi-1's "incoming" state
-    for (long i = hi - 1; i >= lo; i--) {
-      if (i == n - 1) {
-        prev = asnap[i];
-        continue;  // q[n-1] does not exist; prev = a[n-1]
-      }
-      q[i] = prev;
-      prev = fd_add(asnap[i], fd_mul(b, prev));
-    }
-  }
-}
-
-inline Fp pinner(const Fp* a, const Fp* b, long n) {
-  const int T = 16;
-  Fp part[T];
-  long chunk = (n + T - 1) / T;
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-  for (int t = 0; t < T; t++) {
-    long lo = t * chunk, hi = std::min(lo + chunk, n);
-    Fp acc = fd_zero<FpCfg>();
-    for (long i = lo; i < hi; i++) acc = fd_add(acc, fd_mul(a[i], b[i]));
-    part[t] = acc;
-  }
-  Fp out = fd_zero<FpCfg>();
-  for (int t = 0; t < T; t++) out = fd_add(out, part[t]);
-  return out;
-}
-
 // fixed-point window table: [j] holds tab[w][d] = [d * 2^(8w)] P for
 // d in 1..255, w in 0..31 — turns a 255-bit scalar mult of a FIXED point
 // (W, U) into <=32 mixed adds.

@@ -20,6 +20,7 @@
 
 #include "msm.hip"
 #include "ntt.hip"
+#include "openings.hip"
 #include "poseidon.hip"
 #include "binding_sig.hpp"
 #include "tx_wire.hpp"
@@ -361,6 +362,8 @@ void tg_destroy(tg_ctx* ctx) {
   hipStreamSynchronize(c->stream);
   for (PPk* pk : c->ppk_slots) {
     pdev_free(pk->pd);
+    for (Fp* p : pk->d_fixed_coeff) hipFree(p);
+    for (Fp* p : pk->d_sigma_coeff) hipFree(p);
     delete pk;
   }
   c->ppk_slots.clear();
@@ -1366,6 +1369,180 @@ int tg_create_proof_raw(tg_ctx* ctx, const uint8_t* instance, const uint8_t* adv
   int rc = pprove_raw(c, *c->ppk, instance, advice, rng_seed, proof);
   if (rc != 0) return rc;
   return emit_proof(proof, proof_out, cap, out_len);
+}
+
+}  /* extern "C" */
+
+// ---------- diagnostics: the opening-phase kernels on caller data ----------
+
+// canonical LE caller bytes -> Montgomery host vector; false if any is >= p
+static bool diag_to_mont(const uint8_t* src, size_t count, std::vector<Fp>& out) {
+  out.resize(count);
+  for (size_t i = 0; i < count; i++) {
+    Fp v;
+    memcpy(v.l, src + 32 * i, 32);
+    if (!fd_is_canonical(v)) return false;
+    out[i] = fd_to_mont(v);
+  }
+  return true;
+}
+
+static void diag_from_mont(const std::vector<Fp>& in, uint8_t* dst) {
+  for (size_t i = 0; i < in.size(); i++) {
+    Fp v = fd_from_mont(in[i]);
+    memcpy(dst + 32 * i, v.l, 32);
+  }
+}
+
+// a device copy of a Montgomery host vector (at least one element long)
+static hipError_t diag_upload(Ctx* c, DevTmp<Fp>& d, const std::vector<Fp>& h) {
+  hipError_t e = d.alloc(std::max<size_t>(1, h.size()));
+  if (e != hipSuccess) return e;
+  return hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(Fp), hipMemcpyHostToDevice,
+                        c->stream);
+}
+
+// the diagnostics' own staging, released on every way out
+struct DiagDev {
+  ProverDev pd;
+  ~DiagDev() { pdev_free(pd); }
+};
+
+extern "C" {
+
+int tg_fp_poly_eval_batch(tg_ctx* ctx, const uint8_t* coeffs, size_t n_coeffs,
+                          const uint64_t* offs, const uint64_t* lens,
+                          const uint8_t* points, size_t nq, uint8_t* out) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  if (!nq) return TG_ERR_BADARG;
+  std::vector<Fp> h, pts;
+  if (!diag_to_mont(coeffs, n_coeffs, h) || !diag_to_mont(points, nq, pts))
+    return TG_ERR_ENCODING;
+  DevTmp<Fp> d;
+  hipError_t e = diag_upload(c, d, h);
+  if (e != hipSuccess) return set_err(c, "eval upload", e);
+  std::vector<EvalQuery> qs(nq);
+  for (size_t q = 0; q < nq; q++) {
+    if (offs[q] > n_coeffs || lens[q] > n_coeffs - offs[q]) return TG_ERR_BADARG;
+    qs[q] = EvalQuery{d.p + offs[q], (long)lens[q], pts[q]};
+  }
+  DiagDev dd;
+  std::vector<Fp> evs(nq);
+  int rc = dev_poly_eval_batch(c, dd.pd, qs, evs.data());
+  if (rc) return rc;
+  if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_err(c, "eval", e);
+  diag_from_mont(evs, out);
+  return TG_OK;
+}
+
+int tg_fp_kate_div(tg_ctx* ctx, uint8_t* coeffs, size_t len, const uint8_t* points,
+                   size_t npts) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  if (!len || !npts || npts > len) return TG_ERR_BADARG;
+  std::vector<Fp> h, pts;
+  if (!diag_to_mont(coeffs, len, h) || !diag_to_mont(points, npts, pts))
+    return TG_ERR_ENCODING;
+  DevTmp<Fp> d_src, d_dst;
+  hipError_t e = diag_upload(c, d_src, h);
+  if (e == hipSuccess) e = d_dst.alloc(len);
+  if (e != hipSuccess) return set_err(c, "kate upload", e);
+  DiagDev dd;
+  // as in multiopen: the first division leaves its source alone, the
+  // following ones run in place on a vector one shorter each time
+  for (size_t j = 0; j < npts; j++) {
+    std::vector<KateJob> job{
+        KateJob{j == 0 ? d_src.p : d_dst.p, d_dst.p, (long)(len - j), pts[j]}};
+    int rc = dev_kate_div(c, dd.pd, job);
+    if (rc) return rc;
+  }
+  hipMemcpyAsync(h.data(), d_dst.p, len * sizeof(Fp), hipMemcpyDeviceToHost, c->stream);
+  if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_err(c, "kate", e);
+  diag_from_mont(h, coeffs);
+  return TG_OK;
+}
+
+int tg_fp_horner_comb(tg_ctx* ctx, const uint8_t* polys, size_t np, size_t n,
+                      const uint8_t challenge[32], uint8_t* out) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  if (!np || !n) return TG_ERR_BADARG;
+  std::vector<Fp> h, ch;
+  if (!diag_to_mont(polys, np * n, h) || !diag_to_mont(challenge, 1, ch))
+    return TG_ERR_ENCODING;
+  DevTmp<Fp> d, d_out;
+  hipError_t e = diag_upload(c, d, h);
+  if (e == hipSuccess) e = d_out.alloc(n);
+  if (e != hipSuccess) return set_err(c, "comb upload", e);
+  std::vector<const Fp*> ptrs(np);
+  for (size_t j = 0; j < np; j++) ptrs[j] = d.p + j * n;
+  DiagDev dd;
+  int rc = dev_horner_comb(c, dd.pd, ptrs, ch[0], d_out.p, (long)n);
+  if (rc) return rc;
+  std::vector<Fp> res(n);
+  hipMemcpyAsync(res.data(), d_out.p, n * sizeof(Fp), hipMemcpyDeviceToHost, c->stream);
+  if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return set_err(c, "comb", e);
+  diag_from_mont(res, out);
+  return TG_OK;
+}
+
+int tg_ipa_open_probe(tg_ctx* ctx, uint32_t k, const uint8_t* poly, const uint8_t x3[32],
+                      const uint8_t* challenges, const uint8_t* round_blinds,
+                      const uint8_t blind[32], uint8_t* lr_out, uint8_t a_out[32],
+                      uint8_t blind_out[32]) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  if (c->k < 0) return TG_ERR_NOSRS;
+  if (k < 1 || (int)k > c->k) return TG_ERR_BADARG;
+  size_t n = (size_t)1 << k;
+  std::vector<Fp> pp, pt, us, rb, b0;
+  if (!diag_to_mont(poly, n, pp) || !diag_to_mont(x3, 1, pt) ||
+      !diag_to_mont(challenges, k, us) || !diag_to_mont(round_blinds, 2 * (size_t)k, rb) ||
+      !diag_to_mont(blind, 1, b0))
+    return TG_ERR_ENCODING;
+  for (const Fp& u : us)
+    if (fd_is_zero(u)) return TG_ERR_BADARG;
+  DevTmp<Fp> d_pp, d_bvec, d_wfold;
+  hipError_t e = diag_upload(c, d_pp, pp);
+  if (e == hipSuccess) e = d_bvec.alloc(n);
+  if (e == hipSuccess) e = d_wfold.alloc(n);
+  if (e != hipSuccess) return set_err(c, "ipa probe upload", e);
+  fill_powers_launch(d_bvec.p, (long)n, pt[0], c->stream);
+  hipLaunchKernelGGL(k_fill_const, dim3(opn_grid((long)n)), dim3(256), 0, c->stream,
+                     d_wfold.p, (long)n, fd_one_mont<FpCfg>());
+  FixedMulTab utab, wtab;
+  utab.init(c->h_u);
+  wtab.init(c->h_w);
+  DiagDev dd;
+  Fp blind_acc = b0[0], a_final;
+  int round = 0;
+  auto put_point = [](uint8_t* dst, const VestaAff& p) {
+    if (aff_is_identity(p)) {
+      memset(dst, 0, 64);
+      return;
+    }
+    Fq x = fd_from_mont(p.x), y = fd_from_mont(p.y);
+    memcpy(dst, x.l, 32);
+    memcpy(dst + 32, y.l, 32);
+  };
+  int rc = ipa_rounds_dev(
+      c, dd.pd, (int)k, d_pp.p, d_bvec.p, d_wfold.p, utab, wtab, blind_acc, a_final,
+      [&](Fp& l_rand, Fp& r_rand) {
+        l_rand = rb[2 * round];
+        r_rand = rb[2 * round + 1];
+      },
+      [&](const VestaAff& La, const VestaAff& Ra, Fp& uch) {
+        put_point(lr_out + 128 * (size_t)round, La);
+        put_point(lr_out + 128 * (size_t)round + 64, Ra);
+        uch = us[round++];
+        return 0;
+      },
+      [](int) {});
+  if (rc) return rc;
+  diag_from_mont({a_final}, a_out);
+  diag_from_mont({blind_acc}, blind_out);
+  return TG_OK;
 }
 
 }  /* extern "C" */
