@@ -12,8 +12,10 @@
 //   3. k_scatter      : counting-sort point indices by bucket
 //   4. k_bucket_acc   : one thread per bucket, mixed adds (gathers 64 B
 //                       affine points — the ceil(255/w)*n*68 B bytes model)
-//   5. k_bucket_reduce: per-segment suffix sums -> (V + a*W) partials
-//   6. k_final        : partials -> window sums -> double-and-add combine
+//   5. k_bucket_segsum: per-segment running sums (tot, Y), reduced per
+//                       256-segment chunk to T, S and the bit planes of Y
+//   6. k_window_sum   : chunk results -> window sums (the host shim does
+//                       the double-and-add combine of the windows)
 //
 // Scalars arrive in canonical (standard) form — digit extraction needs no
 // Montgomery conversion. Points live device-resident as Montgomery affine
@@ -40,7 +42,9 @@ constexpr int MSM_NWIN_MAX = 16;             // ceil(255/16) (alloc worst case
 constexpr int MSM_NBUCK_MAX = 1 << (MSM_C_MAX - 1);
 constexpr int MSM_SEG = 16;                  // seg len of the LARGE-c config
 struct MsmCfg {
-  int c, nwin, nbuck, nseg, seg;
+  int c, nwin, nbuck, nseg, seg;  // the reduction picks its own segment
+                                  // length (msm_red_seg); nseg/seg remain
+                                  // for the pinned table only
 };
 inline MsmCfg msm_cfg(long n) {
   if (n >= (1L << 18))
@@ -379,53 +383,156 @@ __global__ void __launch_bounds__(MSM_BIG_LANES, 1) k_bucket_acc_big(const uint3
   }
 }
 
-// segment reduce: for window w, segment g over buckets [g*SEG, (g+1)*SEG):
-// partial = sum_{d in seg} (local_d+1)*B + (g*SEG)*W  where W = sum B.
-__global__ void __launch_bounds__(256, 1) k_bucket_reduce(const VestaJac* buckets, VestaJac* partials,
-                       u64 total_windows /* = nwin * batch */, MsmCfg cfg) {
-  u64 t = blockIdx.x * (u64)blockDim.x + threadIdx.x;
-  u64 ntot = total_windows * cfg.nseg;
-  for (; t < ntot; t += (u64)gridDim.x * blockDim.x) {
-    u64 w = t / cfg.nseg;
-    u64 g = t % cfg.nseg;
-    const VestaJac* B = buckets + w * (u64)cfg.nbuck + g * (u64)cfg.seg;
-    VestaJac run = jac_identity<FqCfg>();
-    VestaJac tot = jac_identity<FqCfg>();
-    for (int d = cfg.seg - 1; d >= 0; d--) {
-      run = jac_add(run, B[d]);
-      tot = jac_add(tot, run);
-    }
-    // tot = sum (local_d+1) * B ; add base offset: (g*SEG) * run
-    u64 a = (u64)g * cfg.seg;
-    // double-and-add small scalar a (< 2^15)
-    VestaJac am = jac_identity<FqCfg>();
-    VestaJac base = run;
-    while (a) {
-      if (a & 1) am = jac_add(am, base);
-      base = jac_dbl(base);
-      a >>= 1;
-    }
-    partials[t] = jac_add(tot, am);
+// ---- bucket reduction: window sum W = sum_d (d+1)*B_d, additions only ----
+// With d = s*j + q (segments of s buckets, M = nbuck/s of them per window):
+//   W = sum_j tot_j + s*F(Y),  tot_j = sum_q (q+1)*B_{sj+q},  Y_j = sum_q B_{sj+q},
+//   F(Y) = sum_j j*Y_j.
+// Level 1 (k_bucket_segsum): a block takes a chunk of Wd = min(M, 256)
+// consecutive segments, one lane per segment (tot_j, Y_j by running sums),
+// and reduces the chunk in LDS to T = sum tot, S = sum Y and the bit planes
+// P_b = sum_{t: bit b of t set} Y_t of the lane index t. The planes fall out
+// of ONE folding tree (msm_wtree_active): folding the upper half of the live
+// range onto the lower half leaves the upper half intact, and its plain sum is
+// the plane of that bit. Level 2 (k_window_sum, one block per window) adds
+// the K = M/Wd chunks up: with j = Wd*k + t,
+//   F = sum_b 2^b * sum_k P_{k,b} + Wd * sum_a 2^a * sum_{k: bit a set} S_k.
+// So every weight is applied by doublings once per window, never per segment.
+// All of it uses the complete jac_add/jac_dbl: empty buckets, repeated bases
+// and the zero halves of the IPA vectors make identity, P+P and P+(-P)
+// operands routine here.
+
+// level-1 segment length, chosen per bucket-space size for depth against
+// parallelism (independent of MsmCfg::seg, which only the tests' table pins)
+TG_HD int msm_red_seg(int nbuck) { return nbuck <= 1024 ? 2 : (nbuck <= 4096 ? 4 : 16); }
+
+// level 1, one segment B[0..s): tot = sum (q+1)*B[q], y = sum B[q]
+TG_HD void msm_seg_sums(const VestaJac* B, int s, VestaJac& tot, VestaJac& y) {
+  VestaJac run = B[s - 1];
+  VestaJac t = run;
+  for (int d = s - 2; d >= 0; d--) {
+    run = jac_add(run, B[d]);
+    t = jac_add(t, run);
   }
+  tot = t;
+  y = run;
 }
 
-// per-window tree reduce: block w reduces its MSM_NSEG partials to one
-// Jacobian window sum (the 16 window sums go to the host shim, which does
-// the O(1) 240-doubling Horner combine with the same TG_HD primitives —
-// that serial tail is host work, not a 1-lane GPU kernel).
-__global__ void __launch_bounds__(256) k_wsum(const VestaJac* partials, VestaJac* wsums, MsmCfg cfg) {
-  __shared__ VestaJac lds[256];
-  int w = blockIdx.x;
-  int t = threadIdx.x;  // 256 threads
-  VestaJac acc = jac_identity<FqCfg>();
-  for (int g = t; g < cfg.nseg; g += 256) acc = jac_add(acc, partials[w * cfg.nseg + g]);
-  lds[t] = acc;
+constexpr int MSM_WS_WIDTH = 256;  // segments per chunk = lanes of a level-1 block
+constexpr int MSM_WS_KMAX = 8;     // chunks per window at most (c=16: 2048 segments)
+constexpr int MSM_CHUNK_OUT = 10;  // points a chunk hands on: T, S, P_0..P_7
+constexpr int MSM_WS_TERMS = 16;   // level-2 sum: T, <= 8 planes, <= 3 chunk-index planes
+
+TG_HD int msm_ws_width(int M) { return M < MSM_WS_WIDTH ? M : MSM_WS_WIDTH; }
+TG_HD int msm_lg2(int v) {
+  int l = 0;
+  while ((1 << l) < v) l++;
+  return l;
+}
+
+// level 1, lane tid of chunk q = w*K + k (window w of the batch, chunk k):
+// segment k*Wd + tid of that window into T[tid], C[tid]
+TG_HD void msm_chunk_load(const VestaJac* buckets, int nbuck, int s, u64 q, int tid, VestaJac* C,
+                          VestaJac* T) {
+  const int M = nbuck / s, Wd = msm_ws_width(M), K = M / Wd;
+  if (tid >= Wd) return;
+  u64 w = q / K, k = q % K;
+  msm_seg_sums(buckets + w * (u64)nbuck + (k * Wd + tid) * (u64)s, s, T[tid], C[tid]);
+}
+
+// folding tree with bit planes: at step off, slot i takes slot i+off iff its
+// bits at and above off are zero (the fold of [0, 2*off)) or a single bit
+// above off (the plain sum of an upper half [2^b, 2^(b+1)) left by an earlier
+// fold). After the off=1 step slot 2^b holds P_b and slot 0 the total.
+// A slot that is read in a step has bit off set, so it is not written in it.
+TG_HD bool msm_wtree_active(int i, int off) {
+  int hi = i & ~(off - 1);
+  return (hi & (hi - 1)) == 0 && (hi & off) == 0;
+}
+
+// level 1, one tree step for lane tid of the 256: the plane tree on C, and
+// the plain tree on T in lanes the plane tree never uses at this step (the
+// upper half at off=128, else lanes 192..255, whose two top bits are set),
+// so that no wave runs both
+TG_HD void msm_chunk_step(VestaJac* C, VestaJac* T, int Wd, int off, int tid) {
+  if (tid < Wd && msm_wtree_active(tid, off)) C[tid] = jac_add(C[tid], C[tid + off]);
+  const int base = MSM_WS_WIDTH - (off > 64 ? off : 64);
+  if (tid >= base && tid - base < off) T[tid - base] = jac_add(T[tid - base], T[tid - base + off]);
+}
+
+// level 1, lane tid < 2 + log2(Wd) stores one of the chunk's results
+TG_HD void msm_chunk_store(const VestaJac* C, const VestaJac* T, int Wd, u64 q, int tid,
+                           VestaJac* partials) {
+  if (tid >= 2 + msm_lg2(Wd)) return;
+  partials[q * MSM_CHUNK_OUT + tid] = tid == 0 ? T[0] : (tid == 1 ? C[0] : C[1 << (tid - 2)]);
+}
+
+// level 2, lane = 8*e + k: chunk k's summand of term e of
+//   W = sum_k T_k + s * (sum_b 2^b * sum_k P_{k,b} + Wd * sum_a 2^a * sum_{k: bit a} S_k)
+// (e = 0: T; e = 1..lgw: plane e-1; e = lgw+1+a: chunk-index plane a)
+TG_HD VestaJac msm_wsum_input(const VestaJac* chunks, int Wd, int K, int lane) {
+  const int e = lane >> 3, k = lane & (MSM_WS_KMAX - 1);
+  const int lgw = msm_lg2(Wd), lgk = msm_lg2(K);
+  const VestaJac* c = chunks + k * MSM_CHUNK_OUT;
+  if (k >= K) return jac_identity<FqCfg>();
+  if (e == 0) return c[0];
+  if (e <= lgw) return c[1 + e];
+  int a = e - lgw - 1;
+  if (a < lgk && ((k >> a) & 1)) return c[1];
+  return jac_identity<FqCfg>();
+}
+
+// level 2: term e, summed over the chunks, times its power of two (lgs = log2 s)
+TG_HD VestaJac msm_wsum_scale(VestaJac v, int Wd, int K, int lgs, int e) {
+  // plane e-1 weighs 2^(e-1); chunk-index plane a = e-lgw-1 weighs Wd * 2^a
+  const int nterms = 1 + msm_lg2(Wd) + msm_lg2(K);
+  const int ndbl = (e >= 1 && e < nterms) ? e - 1 + lgs : 0;
+  for (int i = 0; i < ndbl; i++) v = jac_dbl(v);
+  return v;
+}
+
+// level 1: one block per chunk; chunk q's MSM_CHUNK_OUT results go to
+// partials[q * MSM_CHUNK_OUT ..]. 48 KB of LDS: three blocks per CU.
+__global__ void __launch_bounds__(MSM_WS_WIDTH, 1) k_bucket_segsum(const VestaJac* buckets,
+                                                                   VestaJac* partials, int nbuck,
+                                                                   int s) {
+  __shared__ VestaJac lds[2 * MSM_WS_WIDTH];
+  VestaJac* C = lds;
+  VestaJac* T = lds + MSM_WS_WIDTH;
+  const int tid = threadIdx.x;
+  const int Wd = msm_ws_width(nbuck / s);
+  msm_chunk_load(buckets, nbuck, s, blockIdx.x, tid, C, T);
   __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) {
-    if (t < off) lds[t] = jac_add(lds[t], lds[t + off]);
+  for (int off = Wd / 2; off >= 1; off >>= 1) {
+    msm_chunk_step(C, T, Wd, off, tid);
     __syncthreads();
   }
-  if (t == 0) wsums[w] = lds[0];
+  msm_chunk_store(C, T, Wd, blockIdx.x, tid, partials);
+}
+
+// level 2: block w turns window w's K chunk results into one Jacobian window
+// sum (the window sums go to the host shim, which does the O(1) Horner
+// combine with the same TG_HD primitives)
+__global__ void __launch_bounds__(MSM_WS_TERMS* MSM_WS_KMAX) k_window_sum(const VestaJac* partials,
+                                                                          VestaJac* wsums, int Wd,
+                                                                          int K, int lgs) {
+  __shared__ VestaJac X[MSM_WS_TERMS * MSM_WS_KMAX];
+  const int tid = threadIdx.x, k = tid & (MSM_WS_KMAX - 1), e = tid >> 3;
+  X[tid] = msm_wsum_input(partials + (u64)blockIdx.x * K * MSM_CHUNK_OUT, Wd, K, tid);
+  __syncthreads();
+  for (int off = K / 2; off >= 1; off >>= 1) {
+    if (k < off) X[tid] = jac_add(X[tid], X[tid + off]);
+    __syncthreads();
+  }
+  VestaJac v = jac_identity<FqCfg>();
+  if (k == 0) v = msm_wsum_scale(X[tid], Wd, K, lgs, e);
+  __syncthreads();
+  if (k == 0) X[e] = v;
+  __syncthreads();
+  for (int off = MSM_WS_TERMS / 2; off >= 1; off >>= 1) {
+    if (tid < off) X[tid] = jac_add(X[tid], X[tid + off]);
+    __syncthreads();
+  }
+  if (tid == 0) wsums[blockIdx.x] = X[0];
 }
 
 // synthetic bench bases: out[i] = [k_i] G with k_i a splitmix64-derived
@@ -503,8 +610,11 @@ inline hipError_t msm_work_alloc(MsmWork& w, u64 n_total, u64 batch = 1) {
   if ((e = hipMalloc(&w.d_bsum, (nb1 + (nb1 + 511) / 512 + 1) * 4)) != hipSuccess) return e;
   if ((e = hipMalloc(&w.d_sorted, n_total * 32 * 4)) != hipSuccess) return e;
   if ((e = hipMalloc(&w.d_buckets, m * sizeof(VestaJac))) != hipSuccess) return e;
-  if ((e = hipMalloc(&w.d_partials, (u64)MSM_NWIN_MAX * 2 * batch * MSM_NBUCK_MAX /
-                                        MSM_SEG * sizeof(VestaJac))) != hipSuccess)
+  // MSM_CHUNK_OUT points per level-1 chunk, nwin * batch * K chunks. Worst
+  // case c=16: nwin * K = 16 * 8 = 128 per batch, exactly this; the other
+  // rows have 32, 29, 26 (K=1), 48, 44 (K=2) and 80 (c=13, K=4).
+  if ((e = hipMalloc(&w.d_partials, (u64)MSM_NWIN_MAX * MSM_WS_KMAX * batch * MSM_CHUNK_OUT *
+                                        sizeof(VestaJac))) != hipSuccess)
     return e;
   if ((e = hipMalloc(&w.d_wsums, MSM_NWIN_MAX * 2 * batch * sizeof(VestaJac))) !=
       hipSuccess)
@@ -607,16 +717,18 @@ inline void msm_run(MsmWork& w, const ScalarRepr* d_scalars, u64 n, u64 nn, u64 
       else
         msm_acc_launch<false>(w, m, bases, ord, stream);
     }
+    const int rseg = msm_red_seg(cfg.nbuck);
+    const int rWd = msm_ws_width(cfg.nbuck / rseg);  // segments per chunk
+    const int rK = cfg.nbuck / rseg / rWd;           // chunks per window
     {
       [[maybe_unused]] auto p = prof(MSM_P_REDUCE);
-      hipLaunchKernelGGL(k_bucket_reduce, dim3(msm_grid((u64)cfg.nwin * B * cfg.nseg)),
-                         dim3(256), 0, stream, w.d_buckets, w.d_partials,
-                         (u64)cfg.nwin * B, cfg);
+      hipLaunchKernelGGL(k_bucket_segsum, dim3(cfg.nwin * B * rK), dim3(MSM_WS_WIDTH), 0,
+                         stream, w.d_buckets, w.d_partials, cfg.nbuck, rseg);
     }
     {
       [[maybe_unused]] auto p = prof(MSM_P_WSUM);
-      hipLaunchKernelGGL(k_wsum, dim3(cfg.nwin * B), dim3(256), 0, stream, w.d_partials,
-                         w.d_wsums, cfg);
+      hipLaunchKernelGGL(k_window_sum, dim3(cfg.nwin * B), dim3(MSM_WS_TERMS * MSM_WS_KMAX), 0,
+                         stream, w.d_partials, w.d_wsums, rWd, rK, msm_lg2(rseg));
     }
   }
   hipMemcpyAsync(wsums, w.d_wsums, sizeof(VestaJac) * cfg.nwin * B, hipMemcpyDeviceToHost,
