@@ -288,6 +288,14 @@ int tg_ipa_open_probe(tg_ctx* ctx, uint32_t k, const uint8_t* poly, const uint8_
                       const uint8_t blind[32], uint8_t* lr_out, uint8_t a_out[32],
                       uint8_t blind_out[32]);
 
+/* tg_key_gate_path: how the SELECTED key folds its gate constraints into
+ *   the quotient: 1 = the hf_gates kernel specialized to the circuit at
+ *   keygen (hipRTC), 0 = the generic interpreter in k_h_fold (TG_NO_RTC set
+ *   at keygen, or the specialized kernel could not be compiled or loaded —
+ *   the reason is then on stderr). Proof bytes are the same either way.
+ *   TG_ERR_STATE without a key. */
+int tg_key_gate_path(tg_ctx* ctx);
+
 /* ---- sync ---- */
 int tg_synchronize(tg_ctx* ctx);
 

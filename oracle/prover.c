@@ -173,6 +173,26 @@ static void parse_expr(Expr* e, const uint8_t** p) {
     }
 }
 
+/* engine capacities: same figures as TG_MAX_* in
+ * taiga_amd/csrc/prover_impl.hpp */
+enum {
+    ORC_MAX_GATES = 256, ORC_MAX_FIXED = 64, ORC_MAX_ADVICE = 16, ORC_MAX_PERM = 32,
+    ORC_MAX_CHUNKS = 8, ORC_MAX_LOOKUPS = 4, ORC_MAX_LK_EXPRS = 4,
+    ORC_MAX_QUERIES = 64, ORC_MAX_INSTANCE_Q = 2,
+    ORC_MAX_COL_POINTS = 4, /* pts[][4]: points one polynomial opens at */
+    ORC_MAX_POINT_SETS = 16 /* set_pts[16][] */
+};
+
+/* no column is queried at more than ORC_MAX_COL_POINTS rotations */
+static int queries_fit(const Query* qs, int nq) {
+    for (int i = 0; i < nq; i++) {
+        int same = 0;
+        for (int j = 0; j < nq; j++) same += qs[j].col == qs[i].col;
+        if (same > ORC_MAX_COL_POINTS) return 0;
+    }
+    return 1;
+}
+
 static Desc* desc_parse(const uint8_t* blob, size_t len) {
     const uint8_t* p = blob;
     if (len < 64 || memcmp(rd(&p, 4), "TGD1", 4) != 0) return NULL;
@@ -200,11 +220,20 @@ static Desc* desc_parse(const uint8_t* blob, size_t len) {
     d->usable = d->n - (d->bf + 1);
     /* capacity guards (must stay <= the static working arrays below;
      * raised for the exact compliance/RL circuits: 95+ gates, 17-21
-     * fixed columns, 16 quotient pieces) */
-    if (d->n_gates > 256 || d->n_fixed > 64 || d->n_advice > 16 ||
-        d->n_perm > 32 || d->n_lookups > 4 || d->n_advice_q > 64 ||
-        d->n_fixed_q > 64 || d->n_instance_q > 8 ||
-        (d->ext_n / d->n) > 32 || d->n_instance > 1) return NULL;
+     * fixed columns, 16 quotient pieces). The figures are the TG_MAX_*
+     * constants of taiga_amd/csrc/prover_impl.hpp: the product and this
+     * oracle accept the same shapes. */
+    if (d->n_gates > ORC_MAX_GATES || d->n_fixed > ORC_MAX_FIXED ||
+        d->n_advice > ORC_MAX_ADVICE || d->n_perm > ORC_MAX_PERM ||
+        d->n_lookups > ORC_MAX_LOOKUPS || d->n_advice_q > ORC_MAX_QUERIES ||
+        d->n_fixed_q > ORC_MAX_QUERIES || d->n_instance_q > ORC_MAX_INSTANCE_Q ||
+        d->n_gates < 0 || d->n_fixed < 0 || d->n_advice < 0 || d->n_lookups < 0 ||
+        d->n_advice_q < 0 || d->n_fixed_q < 0 || d->n_instance_q < 0 ||
+        (d->ext_n / d->n) > 32 || d->n_instance != 1) return NULL;
+    /* permutation product polynomials: permz_*[], pz_eval[], zp[] hold
+     * ORC_MAX_CHUNKS; chunk_len divides below */
+    if (d->n_perm < 1 || d->chunk_len < 1 ||
+        (d->n_perm + d->chunk_len - 1) / d->chunk_len > ORC_MAX_CHUNKS) return NULL;
     d->consts = (fd_limbs*)xmalloc(sizeof(fd_limbs) * (d->n_consts ? d->n_consts : 1));
     for (int i = 0; i < d->n_consts; i++) {
         if (fd_from_bytes(d->consts[i], rd(&p, 32), FP)) return NULL;
@@ -224,6 +253,8 @@ static Desc* desc_parse(const uint8_t* blob, size_t len) {
         d->instance_q[i].col = rd_u32(&p);
         d->instance_q[i].rot = rd_i32(&p);
     }
+    if (!queries_fit(d->advice_q, d->n_advice_q) || !queries_fit(d->fixed_q, d->n_fixed_q) ||
+        !queries_fit(d->instance_q, d->n_instance_q)) return NULL;
     d->perm_cols = (uint32_t(*)[2])xmalloc(8 * (size_t)d->n_perm);
     for (int i = 0; i < d->n_perm; i++) {
         d->perm_cols[i][0] = rd_u32(&p);
@@ -235,6 +266,9 @@ static Desc* desc_parse(const uint8_t* blob, size_t len) {
     for (int i = 0; i < d->n_lookups; i++) {
         d->lookups[i].n_in = rd_u32(&p);
         d->lookups[i].n_tab = rd_u32(&p);
+        /* lk_in/lk_tab hold ORC_MAX_LK_EXPRS expressions on the device side */
+        if (d->lookups[i].n_in < 1 || d->lookups[i].n_in > ORC_MAX_LK_EXPRS ||
+            d->lookups[i].n_tab < 1 || d->lookups[i].n_tab > ORC_MAX_LK_EXPRS) return NULL;
         d->lookups[i].in = (Expr*)xmalloc(sizeof(Expr) * d->lookups[i].n_in);
         d->lookups[i].tab = (Expr*)xmalloc(sizeof(Expr) * d->lookups[i].n_tab);
         for (uint32_t j = 0; j < d->lookups[i].n_in; j++) parse_expr(&d->lookups[i].in[j], &p);
@@ -1639,8 +1673,8 @@ int orc_multiopen_prove(const Pk* pk, tg_transcript* ts, ProofRng* rng,
         fd_copy(evs[pid][j], queries[q].eval);
     }
     /* distinct point sets (exact-sequence match) in first appearance order */
-    fd_limbs set_pts[16][4];
-    int set_n[16];
+    fd_limbs set_pts[ORC_MAX_POINT_SETS][4];
+    int set_n[ORC_MAX_POINT_SETS];
     int n_sets = 0;
     for (int oi = 0; oi < n_order; oi++) {
         int pid = order[oi];
@@ -1653,6 +1687,7 @@ int orc_multiopen_prove(const Pk* pk, tg_transcript* ts, ProofRng* rng,
             if (eq) { found = s; break; }
         }
         if (found < 0) {
+            if (n_sets == ORC_MAX_POINT_SETS) return -190; /* set_pts[] is full */
             found = n_sets++;
             set_n[found] = npts[pid];
             for (int j = 0; j < set_n[found]; j++) fd_copy(set_pts[found][j], pts[pid][j]);
@@ -2236,8 +2271,9 @@ static int orc_verify_core(Pk* pk, const fd_limbs* inst_in, const uint8_t* proof
     orc_ts_squeeze(&ts, x2);
 
     /* group identically to the prover */
-    int order[128], n_order = 0, poly_set[128], npts[128], seen[128];
-    fd_limbs ptsv[128][4], evsv[128][4];
+    /* up to 1 + 16 + 8 + 3*4 + 64 + 32 + 2 = 135 polynomials at the limits */
+    int order[192], n_order = 0, poly_set[192], npts[192], seen[192];
+    fd_limbs ptsv[192][4], evsv[192][4];
     memset(npts, 0, sizeof(npts));
     memset(seen, 0, sizeof(seen));
     for (int q = 0; q < n_queries; q++) {
@@ -2250,8 +2286,8 @@ static int orc_verify_core(Pk* pk, const fd_limbs* inst_in, const uint8_t* proof
         fd_copy(ptsv[pid][j], queries[q].point);
         fd_copy(evsv[pid][j], queries[q].eval);
     }
-    fd_limbs set_pts[16][4];
-    int set_n[16], n_sets = 0;
+    fd_limbs set_pts[ORC_MAX_POINT_SETS][4];
+    int set_n[ORC_MAX_POINT_SETS], n_sets = 0;
     for (int oi = 0; oi < n_order; oi++) {
         int pid = order[oi];
         int found = -1;
@@ -2263,6 +2299,7 @@ static int orc_verify_core(Pk* pk, const fd_limbs* inst_in, const uint8_t* proof
             if (eq) { found = s; break; }
         }
         if (found < 0) {
+            if (n_sets == ORC_MAX_POINT_SETS) return -190; /* set_pts[] is full */
             found = n_sets++;
             set_n[found] = npts[pid];
             for (int j = 0; j < set_n[found]; j++) fd_copy(set_pts[found][j], ptsv[pid][j]);

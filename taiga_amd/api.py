@@ -71,6 +71,7 @@ def load_library():
         lib.tg_poly_download.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32]
         lib.tg_keygen.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         lib.tg_select_key.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.tg_key_gate_path.argtypes = [ctypes.c_void_p]
         lib.tg_create_proof.argtypes = [
             ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
             ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
@@ -288,6 +289,14 @@ class TaigaGpu:
 
     def select_key(self, slot: int):
         self._ck(self._lib.tg_select_key(self._h, slot))
+
+    def key_gate_path(self) -> int:
+        """1 if the selected key folds its gates with the circuit-specialized
+        hf_gates kernel, 0 if with the k_h_fold interpreter."""
+        rc = self._lib.tg_key_gate_path(self._h)
+        if rc < 0:
+            raise TaigaGpuError(rc, (self._lib.tg_error_string(self._h) or b"").decode())
+        return rc
 
     def create_proof(self, inst_seed: bytes, wit_seed: bytes, rng_seed: bytes) -> bytes:
         out = ctypes.create_string_buffer(1 << 16)

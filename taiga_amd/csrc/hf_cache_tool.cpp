@@ -21,13 +21,15 @@ int main(int argc, char** argv) {
       printf("%s: parse failed\n", argv[a]);
       return 1;
     }
-    uint64_t h = hf_desc_hash(d);
-    std::string path = hf_cache_path(h);
+    // same key as hf_rtc_get: desc hash folded with the generated source's
+    // hash, so an object from an older generator is never taken for current
+    std::string src = hf_rtc_source(d);
+    std::string path = hf_cache_path(hf_cache_key(d, src));
     if (std::ifstream(path).good()) {
       printf("%s: cached (%s)\n", argv[a], path.c_str());
       continue;
     }
-    std::vector<char> code = hf_rtc_compile(d);
+    std::vector<char> code = hf_rtc_compile(src);
     if (code.empty()) {
       printf("%s: compile FAILED (interpreter fallback will be used)\n", argv[a]);
       continue;

@@ -137,9 +137,14 @@ __device__ __forceinline__ Fp f_mul(Fp a, Fp b) {
 // half-hour register-allocation spiral; per-gate functions compile in
 // seconds and still keep each gate's queries register-resident with
 // full common-subexpression elimination inside the gate).
-inline std::string hf_rtc_source(const PDesc& d) {
+// Returns the empty string for a desc it cannot express (an unknown op tag,
+// postfix that underflows or does not end at depth 1): pdesc_parse rejects
+// those, and this generator does not rely on that. `prelude` is a parameter
+// so that a test can show the cache key following the generated text.
+inline std::string hf_rtc_source(const PDesc& d,
+                                 const std::string& prelude = hf_rtc_prelude()) {
   std::ostringstream o;
-  o << hf_rtc_prelude();
+  o << prelude;
   o << "__device__ __constant__ Fp CONSTS[" << (d.consts.empty() ? 1 : d.consts.size())
     << "] = {";
   for (size_t i = 0; i < d.consts.size(); i++) {
@@ -170,6 +175,9 @@ inline std::string hf_rtc_source(const PDesc& d) {
     for (size_t gi = g0; gi < g1; gi++)
     for (const auto& op : d.gates[gi].ops)
       if (op.tag == XFIXED || op.tag == XADVICE || op.tag == XINSTANCE) {
+        uint32_t ncols = op.tag == XFIXED ? d.n_fixed
+                         : op.tag == XADVICE ? d.n_advice : d.n_instance;
+        if (op.a >= ncols) return std::string();
         std::array<int, 3> k{(int)op.tag, (int)op.a, op.b};
         bool seen = false;
         for (auto& q : qs)
@@ -179,7 +187,7 @@ inline std::string hf_rtc_source(const PDesc& d) {
     auto qname = [&](uint32_t tag, uint32_t col, int rot) {
       std::ostringstream n;
       n << "q" << tag << "_" << col << "_" << (rot < 0 ? "m" : "p")
-        << (rot < 0 ? -rot : rot);
+        << (rot < 0 ? -(long)rot : (long)rot);
       return n.str();
     };
     for (auto& q : qs) {
@@ -204,6 +212,7 @@ inline std::string hf_rtc_source(const PDesc& d) {
     for (const auto& op : d.gates[gi].ops) {
       switch (op.tag) {
         case XCONST: {
+          if (op.a >= d.consts.size()) return std::string();
           std::ostringstream e;
           e << "CONSTS[" << op.a << "]";
           stk.push_back(e.str());
@@ -217,6 +226,7 @@ inline std::string hf_rtc_source(const PDesc& d) {
         case XADD:
         case XSUB:
         case XMUL: {
+          if (stk.size() < 2) return std::string();
           std::string b = stk.back(); stk.pop_back();
           std::string a = stk.back(); stk.pop_back();
           const char* fn = op.tag == XADD ? "f_add" : op.tag == XSUB ? "f_sub" : "f_mul";
@@ -224,11 +234,13 @@ inline std::string hf_rtc_source(const PDesc& d) {
           break;
         }
         case XNEG: {
+          if (stk.empty()) return std::string();
           std::string a = stk.back(); stk.pop_back();
           stk.push_back(emit("f_neg(" + a + ")"));
           break;
         }
         case XSCALE: {
+          if (stk.empty() || op.a >= d.consts.size()) return std::string();
           std::string a = stk.back(); stk.pop_back();
           std::ostringstream e;
           e << "f_mul(" << a << ",CONSTS[" << op.a << "])";
@@ -239,6 +251,7 @@ inline std::string hf_rtc_source(const PDesc& d) {
           return std::string();
       }
     }
+    if (stk.size() != 1) return std::string();
     o << "  acc = f_add(f_mul(acc, y), " << stk.back() << ");\n";
     }  // gi
     o << "  return acc;\n}\n";
@@ -256,12 +269,19 @@ inline std::string hf_rtc_source(const PDesc& d) {
   return o.str();
 }
 
-// content-hash -> compiled kernel (process-lifetime cache: 8 contexts
-// keygen the same two descs)
-inline uint64_t hf_desc_hash(const PDesc& d) {
-  uint64_t h = 1469598103934665603ULL;
-  for (uint8_t b : d.blob) h = (h ^ b) * 1099511628211ULL;
+// cache key: the desc blob's hash folded with the hash of the generated
+// source text, so a change to the generator or its prelude can never load
+// a code object compiled from older text (process cache and disk cache)
+inline uint64_t hf_fnv(const void* data, size_t n, uint64_t h = 1469598103934665603ULL) {
+  const uint8_t* b = (const uint8_t*)data;
+  for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ULL;
   return h;
+}
+
+inline uint64_t hf_desc_hash(const PDesc& d) { return hf_fnv(d.blob.data(), d.blob.size()); }
+
+inline uint64_t hf_cache_key(const PDesc& d, const std::string& src) {
+  return hf_fnv(src.data(), src.size(), hf_desc_hash(d));
 }
 
 inline std::string hf_cache_path(uint64_t h) {
@@ -272,17 +292,18 @@ inline std::string hf_cache_path(uint64_t h) {
   return buf;
 }
 
-// compile the desc's gate kernel; returns the code object (empty on
+// compile generated gate-kernel source; returns the code object (empty on
 // failure). Pure hiprtc — usable without a GPU (the build container
 // pre-compiles and ships the .hsaco files so GPU boxes never pay the
 // ~1.5-3 min compile).
-inline std::vector<char> hf_rtc_compile(const PDesc& d) {
-  std::string src = hf_rtc_source(d);
+inline std::vector<char> hf_rtc_compile(const std::string& src) {
   if (src.empty()) return {};
   hiprtcProgram prog;
   if (hiprtcCreateProgram(&prog, src.c_str(), "hf_gates.hip", 0, nullptr, nullptr) !=
-      HIPRTC_SUCCESS)
+      HIPRTC_SUCCESS) {
+    fprintf(stderr, "taiga hf_rtc: hiprtcCreateProgram failed, using interpreter\n");
     return {};
+  }
   const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
   hiprtcResult rc = hiprtcCompileProgram(prog, 3, opts);
   if (rc != HIPRTC_SUCCESS) {
@@ -308,7 +329,9 @@ inline HfRtcKernel* hf_rtc_get(const PDesc& d) {
   static std::map<uint64_t, HfRtcKernel> cache;
   if (getenv("TG_NO_RTC")) return nullptr;
   std::lock_guard<std::mutex> lk(mu);
-  uint64_t h = hf_desc_hash(d);
+  std::string src = hf_rtc_source(d);
+  if (src.empty()) return nullptr;
+  uint64_t h = hf_cache_key(d, src);
   auto it = cache.find(h);
   if (it != cache.end()) return it->second.ready ? &it->second : nullptr;
   HfRtcKernel& k = cache[h];  // default: not ready (negative-cache failures)
@@ -326,7 +349,7 @@ inline HfRtcKernel* hf_rtc_get(const PDesc& d) {
     }
   }
   if (code.empty()) {
-    code = hf_rtc_compile(d);
+    code = hf_rtc_compile(src);
     if (code.empty()) return nullptr;
     FILE* f = fopen(hf_cache_path(h).c_str(), "wb");
     if (f) {
@@ -334,8 +357,12 @@ inline HfRtcKernel* hf_rtc_get(const PDesc& d) {
       fclose(f);
     }
   }
-  if (hipModuleLoadData(&k.mod, code.data()) != hipSuccess) return nullptr;
-  if (hipModuleGetFunction(&k.fn, k.mod, "hf_gates") != hipSuccess) return nullptr;
+  if (hipModuleLoadData(&k.mod, code.data()) != hipSuccess ||
+      hipModuleGetFunction(&k.fn, k.mod, "hf_gates") != hipSuccess) {
+    fprintf(stderr, "taiga hf_rtc: code object %s did not load, using interpreter\n",
+            hf_cache_path(h).c_str());
+    return nullptr;
+  }
   k.ready = true;
   return &k;
 }

@@ -351,9 +351,9 @@ static int gpu_msm_commit(Ctx* c, ProverDev& pd, const Fp* mont_scalars, long nn
 
 
 // ---------------- device h-fold (quotient evaluation on the ext coset) ----
-// The TGD1 postfix expressions have stack depth <= 4 (tools/gen_cs1.py
-// emits left-leaning folds); the device interpreter keeps the stack in four
-// named registers (runtime-indexed arrays would go to scratch — guide rule).
+// The TGD1 postfix expressions have stack depth <= TG_MAX_STACK (pdesc_parse
+// checks it); the device interpreter keeps the stack in that many named
+// registers s0..s7 (runtime-indexed arrays would go to scratch — guide rule).
 
 struct DevExpr {
   int off, len;
@@ -369,7 +369,8 @@ struct DevQuery {
   int col;
   int rot;
 };
-constexpr int HF_MAX_Q = 64;
+constexpr int HF_MAX_Q = TG_MAX_QUERIES;
+static_assert(TG_MAX_STACK == 8, "DSTK_* keep the stack in registers s0..s7");
 
 struct HFoldArgs {
   long ext_n, rs;
@@ -378,24 +379,41 @@ struct HFoldArgs {
   const Fp *x_ext, *l0, *llast, *lactive, *t_inv;
   const ExprOp* ops;
   const Fp* consts;
-  DevExpr gates[256];
-  int lk_nin[4], lk_ntab[4];
-  DevExpr lk_in[4][4], lk_tab[4][4];
-  const Fp* fixed_cols[64];
-  const Fp* advice_cols[12];
-  const Fp* inst_cols[2];
-  const Fp* sigma[32];
-  int perm_kind[32], perm_idx[32];
-  Fp dpow[32];
-  const Fp* zp[8];
-  const Fp* lkz[4];
-  const Fp* lkap[4];
-  const Fp* lksp[4];
+  // every array below is sized by the limit pdesc_parse enforces
+  DevExpr gates[TG_MAX_GATES];
+  int lk_nin[TG_MAX_LOOKUPS], lk_ntab[TG_MAX_LOOKUPS];
+  DevExpr lk_in[TG_MAX_LOOKUPS][TG_MAX_LK_EXPRS], lk_tab[TG_MAX_LOOKUPS][TG_MAX_LK_EXPRS];
+  const Fp* fixed_cols[TG_MAX_FIXED];
+  const Fp* advice_cols[TG_MAX_ADVICE];
+  const Fp* inst_cols[TG_MAX_INSTANCE];
+  const Fp* sigma[TG_MAX_PERM];
+  int perm_kind[TG_MAX_PERM], perm_idx[TG_MAX_PERM];
+  Fp dpow[TG_MAX_PERM];
+  const Fp* zp[TG_MAX_CHUNKS];
+  const Fp* lkz[TG_MAX_LOOKUPS];
+  const Fp* lkap[TG_MAX_LOOKUPS];
+  const Fp* lksp[TG_MAX_LOOKUPS];
   Fp* out;
   const DevQuery* queries;  // combined [fixed_q..., advice_q..., instance_q...]
   int n_queries;
   const Fp* acc_init;  // pre-folded gate accumulator (RTC path), or null
 };
+#define HF_CAP(field, cap)                                                    \
+  static_assert(sizeof(HFoldArgs::field) / sizeof(((HFoldArgs*)0)->field[0]) == \
+                    (size_t)(cap),                                              \
+                "HFoldArgs::" #field " and its pdesc_parse guard disagree")
+HF_CAP(gates, TG_MAX_GATES);
+HF_CAP(fixed_cols, TG_MAX_FIXED);
+HF_CAP(advice_cols, TG_MAX_ADVICE);
+HF_CAP(inst_cols, TG_MAX_INSTANCE);
+HF_CAP(sigma, TG_MAX_PERM);
+HF_CAP(dpow, TG_MAX_PERM);
+HF_CAP(zp, TG_MAX_CHUNKS);
+HF_CAP(lkz, TG_MAX_LOOKUPS);
+HF_CAP(lk_in, TG_MAX_LOOKUPS);
+HF_CAP(lk_in[0], TG_MAX_LK_EXPRS);
+HF_CAP(lk_tab[0], TG_MAX_LK_EXPRS);
+#undef HF_CAP
 
 #define DSTK_PUSH(v)                                   \
   do {                                                 \
@@ -782,7 +800,7 @@ static int ppk_keygen(Ctx* c, PPk& pk, const uint8_t* desc, size_t desc_len) {
     if (up_ext(pk.lactive_ext, pk.d_lactive)) return TG_ERR_NOMEM;
     if (up_ext(pk.t_inv_ext, pk.d_tinv)) return TG_ERR_NOMEM;
     if (up_ext(pk.x_ext, pk.d_xext)) return TG_ERR_NOMEM;
-    // flatten + upload expressions; verify interpreter stack depth <= 4
+    // flatten + upload expressions (stack depth re-checked against DSTK)
     std::vector<ExprOp> flat;
     // query table: [fixed_q..., advice_q..., instance_q...] — the h-fold
     // kernel preloads these per row; gate/lookup ops are rewritten to
@@ -833,7 +851,7 @@ static int ppk_keygen(Ctx* c, PPk& pk, const uint8_t* desc, size_t desc_len) {
         else if (op.tag == XADD || op.tag == XSUB || op.tag == XMUL) depth--;
         if (depth > maxd) maxd = depth;
       }
-      if (maxd > 8) return DevExpr{-1, -1};  // DSTK register stack depth
+      if (maxd > TG_MAX_STACK) return DevExpr{-1, -1};  // DSTK register stack depth
       DevExpr de{(int)flat.size(), (int)e.ops.size()};
       for (ExprOp op : e.ops) {
         if (op.tag == XFIXED || op.tag == XADVICE || op.tag == XINSTANCE) {
@@ -1476,7 +1494,7 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   }
   std::vector<Fp> adv_eval(d.n_advice_q), fix_eval(d.n_fixed_q), sig_eval(d.n_perm);
   Fp rand_eval, h_eval;
-  Fp pz_eval[8][2], pz_last_eval[8], lk_eval[4][5];
+  Fp pz_eval[TG_MAX_CHUNKS][2], pz_last_eval[TG_MAX_CHUNKS], lk_eval[TG_MAX_LOOKUPS][5];
   std::vector<Fp> inst_eval(d.n_instance_q);
   Fp x_next = rot_pt(x, 1), x_prev = rot_pt(x, -1), x_last = rot_pt(x, -(d.bf + 1));
   {
@@ -1820,7 +1838,7 @@ static int pfind_q(const std::vector<PQuery>& qs, uint32_t col, int32_t rot) {
 }
 
 static bool pexpr_eval_scalar(Fp& out, const PExpr& e, const PScalarCtx& c) {
-  Fp stack[16];
+  Fp stack[TG_MAX_STACK];
   int sp = 0;
   for (const auto& op : e.ops) {
     switch (op.tag) {
@@ -1925,7 +1943,7 @@ static int pverify_guard(Ctx* c, PPk& pk, const std::vector<Fp>& inst_lag,
 
   std::vector<Fp> adv_eval(d.n_advice_q), fix_eval(d.n_fixed_q), sig_eval(d.n_perm);
   Fp rand_eval;
-  Fp pz_eval[8][2], pz_last_eval[8], lk_eval[4][5];
+  Fp pz_eval[TG_MAX_CHUNKS][2], pz_last_eval[TG_MAX_CHUNKS], lk_eval[TG_MAX_LOOKUPS][5];
   for (int q = 0; q < d.n_advice_q; q++)
     if (!ts.read_scalar(adv_eval[q])) return -110;
   for (int q = 0; q < d.n_fixed_q; q++)
@@ -1960,10 +1978,10 @@ static int pverify_guard(Ctx* c, PPk& pk, const std::vector<Fp>& inst_lag,
   Fp expected_h;
   {
     PScalarCtx sc{&d, adv_eval.data(), fix_eval.data(), inst_eval.data()};
-    Fp gate_vals[256];
+    Fp gate_vals[TG_MAX_GATES];
     for (int g = 0; g < d.n_gates; g++)
       if (!pexpr_eval_scalar(gate_vals[g], d.gates[g], sc)) return -120;
-    Fp perm_colvals[32], sigma_vals[32];
+    Fp perm_colvals[TG_MAX_PERM], sigma_vals[TG_MAX_PERM];
     for (int jj = 0; jj < d.n_perm; jj++) {
       auto [kind, idx] = d.perm_cols[jj];
       int q;
@@ -1982,7 +2000,7 @@ static int pverify_guard(Ctx* c, PPk& pk, const std::vector<Fp>& inst_lag,
       }
       sigma_vals[jj] = sig_eval[jj];
     }
-    Fp lk[4][7];
+    Fp lk[TG_MAX_LOOKUPS][7];
     for (int l = 0; l < nlk; l++) {
       lk[l][0] = lk_eval[l][0];
       lk[l][1] = lk_eval[l][1];
@@ -2010,7 +2028,7 @@ static int pverify_guard(Ctx* c, PPk& pk, const std::vector<Fp>& inst_lag,
     for (long i = d.usable + 1; i < n; i++)
       lblind = fd_add(lblind, plagrange_at(x, i, xn, pk, n));
     Fp lactive = fd_sub(one, fd_add(llast, lblind));
-    Fp zp[8][2], zp_last[8];
+    Fp zp[TG_MAX_CHUNKS][2], zp_last[TG_MAX_CHUNKS];
     for (int ch = 0; ch < nchunks; ch++) {
       zp[ch][0] = pz_eval[ch][0];
       zp[ch][1] = pz_eval[ch][1];

@@ -742,6 +742,13 @@ int tg_select_key(tg_ctx* ctx, int slot) {
   return TG_OK;
 }
 
+int tg_key_gate_path(tg_ctx* ctx) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  if (!c->ppk || !c->ppk->ready) return TG_ERR_STATE;
+  return c->ppk->rtc && c->ppk->rtc->ready ? 1 : 0;
+}
+
 int tg_create_proof(tg_ctx* ctx, const uint8_t inst_seed[32], const uint8_t wit_seed[32],
                     const uint8_t rng_seed[32], uint8_t* proof_out, size_t cap,
                     size_t* out_len) {

@@ -34,6 +34,20 @@ def test_every_header_symbol_exported():
         assert hasattr(lib, n), f"symbol {n} missing from libtaiga_gpu.so"
 
 
+def test_gate_path_entry_point():
+    """tg_key_gate_path is declared, exported and wrapped; without a context
+    it is TG_ERR_BADARG, never a crash"""
+    import taiga_amd
+
+    _build()
+    hdr = open(HDR).read()
+    assert re.search(r"^int tg_key_gate_path\(tg_ctx\* ctx\);", hdr, re.M)
+    lib = taiga_amd.api.load_library()
+    assert lib.tg_key_gate_path.argtypes == [ctypes.c_void_p]
+    assert lib.tg_key_gate_path(None) == -2
+    assert callable(taiga_amd.TaigaGpu.key_gate_path)
+
+
 def test_device_count_callable_without_gpu():
     import taiga_amd
 

@@ -83,6 +83,7 @@ def test_gpu_random_circuit_parity():
             oracle_keygen(lib, desc)
             slot = g.keygen(desc)
             g.select_key(slot)
+            assert g.key_gate_path() == 1, "this suite covers the specialized hf_gates path"
             o_proof = oracle_prove(lib, inst, adv)
             g_proof = g.create_proof_raw(inst, adv, RNG)
             assert g_proof == o_proof, f"seed {seed} ({meta}): proof bytes differ"
