@@ -255,7 +255,8 @@ int tg_ptx_verify(tg_ctx* ctx, int slot_compliance, int slot_rl,
 /* ---- kernel profiling (HIP events on the ctx stream) ----
  * names: "msm_digits", "msm_scan", "msm_scatter", "msm_bucket_acc",
  *        "msm_reduce", "msm_wsum", "ntt_stage", "ntt_fused", "ntt_bitrev",
- *        "ntt_scale", "msm_total", "ntt_total" */
+ *        "ntt_scale", "msm_total", "ntt_total", "gp_terms", "gp_inverse",
+ *        "gp_scan" (the grand-product kernels of a proof) */
 void tg_prof_enable(tg_ctx* ctx, int on);
 void tg_prof_reset(tg_ctx* ctx);
 int tg_prof_get(tg_ctx* ctx, const char* name, double* total_ms, long* count);
@@ -287,6 +288,39 @@ int tg_ipa_open_probe(tg_ctx* ctx, uint32_t k, const uint8_t* poly, const uint8_
                       const uint8_t* challenges, const uint8_t* round_blinds,
                       const uint8_t blind[32], uint8_t* lr_out, uint8_t a_out[32],
                       uint8_t blind_out[32]);
+
+/* ---- diagnostics: the prover's grand-product kernels on caller data ----
+ * Same conventions as above; TG_ERR_BADARG for a null ctx and for zero or
+ * oversized sizes (more than 2^24 elements in one call). Each entry calls
+ * the launchers the prover calls. No SRS is required.
+ * tg_fp_batch_inverse: vals[i] <- vals[i]^-1 in place, i < n; a zero stays
+ *   zero.
+ * tg_fp_prefix_product: ratios holds nseg segments of seg_lens[s] >= 1
+ *   elements, one after the other. For every segment z_s[0] = start_s and
+ *   z_s[i+1] = z_s[i] * ratio_s[i], with start_0 = init and start_{s+1} =
+ *   z_s[seg_lens[s]] (the way the permutation chunks chain). z_out receives
+ *   the seg_lens[s] + 1 values of every segment, segment after segment.
+ * tg_perm_product_probe: the permutation grand products over rows i < u of
+ *   ncols columns of 2^k rows, in chunks of chunk_len columns: values and
+ *   sigmas are ncols x 2^k column-major; omega and delta are derived for k
+ *   as keygen derives them. z_out = nchunks x (u + 1), chunk after chunk,
+ *   chunk 0 starting from 1. 4 <= k <= 15, 1 <= u < 2^k, 1 <= ncols <= 32,
+ *   nchunks <= 8.
+ * tg_lookup_product_probe: the lookup grand product of the compressed
+ *   expressions a, s against their permuted forms ap, sp (2^k rows each):
+ *   z[0] = 1, z[i+1] = z[i] (a_i + beta)(s_i + gamma) /
+ *   ((ap_i + beta)(sp_i + gamma)); z_out = u + 1 elements. */
+int tg_fp_batch_inverse(tg_ctx* ctx, uint8_t* vals, size_t n);
+int tg_fp_prefix_product(tg_ctx* ctx, const uint8_t* ratios, const uint64_t* seg_lens,
+                         size_t nseg, const uint8_t init[32], uint8_t* z_out);
+int tg_perm_product_probe(tg_ctx* ctx, uint32_t k, uint64_t u, uint32_t ncols,
+                          uint32_t chunk_len, const uint8_t* values,
+                          const uint8_t* sigmas, const uint8_t beta[32],
+                          const uint8_t gamma[32], uint8_t* z_out);
+int tg_lookup_product_probe(tg_ctx* ctx, uint32_t k, uint64_t u, const uint8_t* a,
+                            const uint8_t* s, const uint8_t* ap, const uint8_t* sp,
+                            const uint8_t beta[32], const uint8_t gamma[32],
+                            uint8_t* z_out);
 
 /* tg_key_gate_path: how the SELECTED key folds its gate constraints into
  *   the quotient: 1 = the hf_gates kernel specialized to the circuit at

@@ -141,6 +141,17 @@ def load_library():
             ctypes.c_char_p, ctypes.c_char_p]
         lib.tg_ipa_open_probe.argtypes = [
             ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_char_p] * 8
+        # diagnostics (grand-product kernels on caller data)
+        lib.tg_fp_batch_inverse.argtypes = [
+            ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        lib.tg_fp_prefix_product.argtypes = [
+            ctypes.c_void_p, ctypes.c_char_p, u64p, ctypes.c_size_t, ctypes.c_char_p,
+            ctypes.c_char_p]
+        lib.tg_perm_product_probe.argtypes = [
+            ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+            ctypes.c_uint32] + [ctypes.c_char_p] * 5
+        lib.tg_lookup_product_probe.argtypes = [
+            ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64] + [ctypes.c_char_p] * 7
         _lib = lib
     return _lib
 
@@ -414,6 +425,44 @@ class TaigaGpu:
     def witness_hash(self, inst_seed: bytes, wit_seed: bytes) -> bytes:
         out = ctypes.create_string_buffer(32)
         self._ck(self._lib.tg_witness_hash(self._h, inst_seed, wit_seed, out))
+        return out.raw
+
+    # --- grand-product diagnostics (32B LE canonical elements) ---
+    def fp_batch_inverse(self, vals: bytes) -> bytes:
+        """Element-wise inverse of len(vals) // 32 elements; zero stays zero."""
+        buf = ctypes.create_string_buffer(vals, len(vals))
+        self._ck(self._lib.tg_fp_batch_inverse(self._h, buf, len(vals) // 32))
+        return buf.raw
+
+    def fp_prefix_product(self, ratios: bytes, seg_lens, init: bytes) -> bytes:
+        """Chained prefix product: per segment of L ratios the L + 1 values
+        z[0] = start, z[i+1] = z[i] * ratio[i]; the first segment starts from
+        init, each further one from the value the previous one ended with."""
+        lens = (ctypes.c_uint64 * len(seg_lens))(*seg_lens)
+        out = ctypes.create_string_buffer(32 * (sum(seg_lens) + len(seg_lens)))
+        self._ck(self._lib.tg_fp_prefix_product(
+            self._h, ratios, lens, len(seg_lens), init, out))
+        return out.raw
+
+    def perm_product_probe(self, k: int, u: int, ncols: int, chunk_len: int,
+                           values: bytes, sigmas: bytes, beta: bytes,
+                           gamma: bytes) -> bytes:
+        """The permutation grand products of ncols columns of 2^k rows
+        (column-major values and sigmas) in chunks of chunk_len: nchunks
+        vectors of u + 1 elements, chunk after chunk."""
+        nchunks = (ncols + chunk_len - 1) // chunk_len if chunk_len else 0
+        out = ctypes.create_string_buffer(32 * max(1, nchunks * (u + 1)))
+        self._ck(self._lib.tg_perm_product_probe(
+            self._h, k, u, ncols, chunk_len, values, sigmas, beta, gamma, out))
+        return out.raw[: 32 * nchunks * (u + 1)]
+
+    def lookup_product_probe(self, k: int, u: int, a: bytes, s: bytes, ap: bytes,
+                             sp: bytes, beta: bytes, gamma: bytes) -> bytes:
+        """The lookup grand product of A, S against the permuted A', S'
+        (2^k rows each): u + 1 elements."""
+        out = ctypes.create_string_buffer(32 * (u + 1))
+        self._ck(self._lib.tg_lookup_product_probe(
+            self._h, k, u, a, s, ap, sp, beta, gamma, out))
         return out.raw
 
     # --- profiling ---

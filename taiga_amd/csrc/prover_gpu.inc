@@ -26,6 +26,19 @@ struct ProverDev {
   size_t stage_cap = 0;
   Fp* d_small = nullptr;
   size_t small_cap = 0;
+  // grand products (grand_products.hip): n-element slots holding Lagrange
+  // forms, sized from the descriptor at keygen. The sigma columns and the
+  // fixed columns of the permutation are uploaded once per key; per proof
+  // the advice and instance columns, the lookup vectors and the z vectors
+  // live here, where the commits, the grand-product kernels and the
+  // transforms all read them; the last slots hold the flat num / den arrays.
+  Fp* lag = nullptr;
+  int lag_slots = 0;
+  // host copies of the small tables those launchers upload: they must
+  // outlive the stream's next synchronisation
+  GpPermArgs gp_perm_h;
+  GpLookupArgs gp_lk_h;
+  std::vector<uint8_t> gp_scan_h;
   NttPlan plan_n, plan_ext;
   long ext_n = 0, n = 0;
 };
@@ -93,6 +106,7 @@ static void pdev_free(ProverDev& pd) {
   for (Fp* p : pd.ext_pool) hipFree(p);
   pd.ext_pool.clear();
   if (pd.coef) hipFree(pd.coef);
+  if (pd.lag) hipFree(pd.lag);
   if (pd.open_ws) hipFree(pd.open_ws);
   if (pd.d_stage) hipFree(pd.d_stage);
   if (pd.d_small) hipFree(pd.d_small);
@@ -135,11 +149,12 @@ static int gpu_coeff_to_ext(Ctx* c, ProverDev& pd, const Fp* coeff, Fp* ext_out,
 // fused: lagrange(host, Mont) -> coeff, left on device in the coefficient
 // pool slot d_coeff_dst (the openings read it there; it never returns to
 // the host) + extended-coset evals left on device in d_ext_dst
-static int gpu_lag_to_coeff_ext_dev(Ctx* c, ProverDev& pd, const Fp* host_lag,
+static int gpu_lag_to_coeff_ext_dev(Ctx* c, ProverDev& pd, const Fp* lag,
                                     Fp* d_coeff_dst, Fp* d_ext_dst, int k, int ext_k,
-                                    const Fp& ninv, const Fp& zeta) {
+                                    const Fp& ninv, const Fp& zeta,
+                                    hipMemcpyKind from = hipMemcpyHostToDevice) {
   long n = 1L << k, ext_n = 1L << ext_k;
-  hipMemcpyAsync(pd.ws0, host_lag, n * sizeof(Fp), hipMemcpyHostToDevice, c->stream);
+  hipMemcpyAsync(pd.ws0, lag, n * sizeof(Fp), from, c->stream);
   if (ntt_run(pd.ws0, pd.ws1, pd.plan_n, k, true, c->stream, &ninv, ntt_noprof) !=
       hipSuccess)
     return TG_ERR_HIP;
@@ -150,7 +165,16 @@ static int gpu_lag_to_coeff_ext_dev(Ctx* c, ProverDev& pd, const Fp* host_lag,
   if (ntt_run(d_ext_dst, pd.ws1, pd.plan_ext, ext_k, false, c->stream, nullptr,
               ntt_noprof) != hipSuccess)
     return TG_ERR_HIP;
-  return 0;  // host_lag must outlive the stream's next synchronisation
+  return 0;  // a host lag must outlive the stream's next synchronisation
+}
+
+// the same from a Lagrange vector already on the device (a slot of the
+// Lagrange pool), which is left as it is
+static int gpu_dlag_to_coeff_ext_dev(Ctx* c, ProverDev& pd, const Fp* d_lag,
+                                     Fp* d_coeff_dst, Fp* d_ext_dst, int k, int ext_k,
+                                     const Fp& ninv, const Fp& zeta) {
+  return gpu_lag_to_coeff_ext_dev(c, pd, d_lag, d_coeff_dst, d_ext_dst, k, ext_k, ninv,
+                                  zeta, hipMemcpyDeviceToDevice);
 }
 
 // workspace and the canonical-scalar array for B MSMs of nn points each
@@ -269,6 +293,151 @@ static int dev_kate_div(Ctx* c, ProverDev& pd, const std::vector<KateJob>& jobs)
                  c->stream);
   hipLaunchKernelGGL(k_kate_div, dim3((unsigned)jobs.size()), dim3(OPN_T), 0, c->stream,
                      (const KateJob*)dj);
+  return 0;
+}
+
+// ---------------- grand-product launchers (kernels: grand_products.hip) ----
+// Same conventions as the opening-phase launchers above. The host copies of
+// the tables live in pd, so they outlive the stream's next synchronisation.
+
+static_assert(GP_MAX_COLS == TG_MAX_PERM && GP_MAX_CHUNKS == TG_MAX_CHUNKS &&
+                  GP_MAX_LOOKUPS == TG_MAX_LOOKUPS,
+              "grand_products.hip tables and the pdesc_parse limits disagree");
+
+// rows a thread of the term kernels walks
+constexpr int GP_TERM_ROWS = 4;
+static inline unsigned gp_term_grid(long u) {
+  long per = (long)GP_B * GP_TERM_ROWS;
+  return (unsigned)std::max<long>(1, (u + per - 1) / per);
+}
+
+// d_num / d_den [ch * u + i], i < u, for every chunk of chunk_len columns
+static int dev_gp_perm_terms(Ctx* c, ProverDev& pd, const std::vector<const Fp*>& cols,
+                             const std::vector<const Fp*>& sigmas, int chunk_len, long u,
+                             const Fp& beta, const Fp& gamma, const Fp& omega,
+                             const Fp& delta, Fp* d_num, Fp* d_den) {
+  int n_perm = (int)cols.size();
+  if (n_perm < 1 || n_perm > GP_MAX_COLS || sigmas.size() != cols.size() ||
+      chunk_len < 1 || u < 1)
+    return TG_ERR_BADARG;
+  int nchunks = (n_perm + chunk_len - 1) / chunk_len;
+  if (nchunks > GP_MAX_CHUNKS) return TG_ERR_BADARG;
+  GpPermArgs& A = pd.gp_perm_h;
+  A = GpPermArgs{};
+  Fp bd = beta;
+  for (int j = 0; j < n_perm; j++) {
+    A.cols[j] = cols[j];
+    A.sigma[j] = sigmas[j];
+    A.bdpow[j] = bd;
+    bd = fd_mul(bd, delta);
+  }
+  A.beta = beta;
+  A.gamma = gamma;
+  A.omega = omega;
+  A.num = d_num;
+  A.den = d_den;
+  A.u = u;
+  A.n_perm = n_perm;
+  A.chunk_len = chunk_len;
+  GpPermArgs* dA = (GpPermArgs*)pdev_stage(c, pd, sizeof(GpPermArgs));
+  if (!dA) return TG_ERR_NOMEM;
+  hipMemcpyAsync(dA, &A, sizeof(GpPermArgs), hipMemcpyHostToDevice, c->stream);
+  ProfScope ps(c, P_GP_TERMS);
+  hipLaunchKernelGGL(k_gp_perm_terms, dim3(gp_term_grid(u), (unsigned)nchunks), dim3(GP_B),
+                     0, c->stream, (const GpPermArgs*)dA);
+  return 0;
+}
+
+// d_num / d_den [l * u + i], i < u, for every lookup
+static int dev_gp_lookup_terms(Ctx* c, ProverDev& pd, int nlk, const Fp* const* a,
+                               const Fp* const* s, const Fp* const* ap,
+                               const Fp* const* sp, long u, const Fp& beta,
+                               const Fp& gamma, Fp* d_num, Fp* d_den) {
+  if (nlk < 1 || nlk > GP_MAX_LOOKUPS || u < 1) return TG_ERR_BADARG;
+  GpLookupArgs& A = pd.gp_lk_h;
+  A = GpLookupArgs{};
+  for (int l = 0; l < nlk; l++) {
+    A.a[l] = a[l];
+    A.s[l] = s[l];
+    A.ap[l] = ap[l];
+    A.sp[l] = sp[l];
+  }
+  A.beta = beta;
+  A.gamma = gamma;
+  A.num = d_num;
+  A.den = d_den;
+  A.u = u;
+  GpLookupArgs* dA = (GpLookupArgs*)pdev_stage(c, pd, sizeof(GpLookupArgs));
+  if (!dA) return TG_ERR_NOMEM;
+  hipMemcpyAsync(dA, &A, sizeof(GpLookupArgs), hipMemcpyHostToDevice, c->stream);
+  ProfScope ps(c, P_GP_TERMS);
+  hipLaunchKernelGGL(k_gp_lookup_terms, dim3(gp_term_grid(u), (unsigned)nlk), dim3(GP_B), 0,
+                     c->stream, (const GpLookupArgs*)dA);
+  return 0;
+}
+
+// d_v[i] <- d_v[i]^-1, i < count, zeros staying zero: one launch
+static int dev_gp_batch_inverse(Ctx* c, Fp* d_v, long count) {
+  if (count < 1 || gp_blocks_for(count) > 0x7fffffffL) return TG_ERR_BADARG;
+  ProfScope ps(c, P_GP_INVERSE);
+  hipLaunchKernelGGL(k_gp_batch_inverse, dim3((unsigned)gp_blocks_for(count)), dim3(GP_B), 0,
+                     c->stream, d_v, count);
+  return 0;
+}
+
+// one segment of the chained prefix product: len ratios, len + 1 values
+// written to d_dst. A chained segment starts from the value the previous
+// segment ended with, any other from init.
+struct GpSeg {
+  long len;
+  Fp* d_dst;
+  bool chained;
+  Fp init;
+};
+
+// z_s[0] = start value, z_s[i+1] = z_s[i] * ratio_s[i] for every segment;
+// the ratios are d_a[i] * d_b[i] (d_b may be null) over the concatenation
+// of the segments. Three launches whatever the number of segments; the
+// chaining values stay on the device.
+static int dev_gp_scan(Ctx* c, ProverDev& pd, const Fp* d_a, const Fp* d_b,
+                       const std::vector<GpSeg>& segs) {
+  if (segs.empty()) return TG_ERR_BADARG;
+  std::vector<GpScanBlock> blocks;
+  std::vector<GpScanChain> chains;
+  long flat = 0;
+  for (size_t s = 0; s < segs.size(); s++) {
+    const GpSeg& sg = segs[s];
+    if (sg.len < 1) return TG_ERR_BADARG;
+    if (s == 0 || !sg.chained)
+      chains.push_back(GpScanChain{sg.init, (int)blocks.size(), (int)blocks.size()});
+    for (long o = 0; o < sg.len; o += GP_T) {
+      int len = (int)std::min<long>(GP_T, sg.len - o);
+      blocks.push_back(GpScanBlock{flat + o, sg.d_dst + o, len, o + len == sg.len ? 1 : 0});
+    }
+    if (blocks.size() > 0x3fffffff) return TG_ERR_BADARG;
+    chains.back().blk_hi = (int)blocks.size();
+    flat += sg.len;
+  }
+  size_t nb = blocks.size(), bbytes = nb * sizeof(GpScanBlock);
+  size_t cbytes = chains.size() * sizeof(GpScanChain);
+  pd.gp_scan_h.resize(bbytes + cbytes);
+  memcpy(pd.gp_scan_h.data(), blocks.data(), bbytes);
+  memcpy(pd.gp_scan_h.data() + bbytes, chains.data(), cbytes);
+  uint8_t* dt = (uint8_t*)pdev_stage(c, pd, bbytes + cbytes);
+  Fp* d_bp = pdev_small(c, pd, 2 * nb);
+  if (!dt || !d_bp) return TG_ERR_NOMEM;
+  Fp* d_off = d_bp + nb;
+  hipMemcpyAsync(dt, pd.gp_scan_h.data(), bbytes + cbytes, hipMemcpyHostToDevice,
+                 c->stream);
+  const GpScanBlock* dblk = (const GpScanBlock*)dt;
+  const GpScanChain* dch = (const GpScanChain*)(dt + bbytes);
+  ProfScope ps(c, P_GP_SCAN);
+  hipLaunchKernelGGL(k_gp_scan_reduce, dim3((unsigned)nb), dim3(GP_B), 0, c->stream, dblk,
+                     d_a, d_b, d_bp);
+  hipLaunchKernelGGL(k_gp_scan_offsets, dim3((unsigned)chains.size()), dim3(GP_B), 0,
+                     c->stream, dch, (const Fp*)d_bp, d_off);
+  hipLaunchKernelGGL(k_gp_scan_apply, dim3((unsigned)nb), dim3(GP_B), 0, c->stream, dblk,
+                     d_a, d_b, (const Fp*)d_off);
   return 0;
 }
 
@@ -607,6 +776,36 @@ struct PPk {
   bool ready = false;
 };
 
+// Slot numbers of the Lagrange pool (pd.lag), from the descriptor alone:
+//   sigma columns | fixed columns of the permutation      (once per key)
+//   advice | instance | z (chunks, then lookups)          (per proof)
+//   per lookup A', S', A, S | flat num | flat den
+// The advice slots, the z slots and each A', S' pair are contiguous: a
+// batched commit reads them as one concatenation.
+struct LagLayout {
+  int sigma = 0, fixed = 0, adv = 0, inst = 0, z = 0, lk = 0, num = 0, den = 0, total = 0;
+  int nz = 0;
+  std::vector<int> fixed_slot;  // per fixed column, -1 if not permuted
+  explicit LagLayout(const PDesc& d) {
+    int nchunks = (d.n_perm + d.chunk_len - 1) / d.chunk_len;
+    nz = nchunks + d.n_lookups;
+    fixed = sigma + d.n_perm;
+    fixed_slot.assign(d.n_fixed, -1);
+    int nfp = 0;
+    for (int j = 0; j < d.n_perm; j++) {
+      auto [kind, idx] = d.perm_cols[j];
+      if (kind == 1 && fixed_slot[idx] < 0) fixed_slot[idx] = fixed + nfp++;
+    }
+    adv = fixed + nfp;
+    inst = adv + d.n_advice;
+    z = inst + 1;
+    lk = z + nz;
+    num = lk + 4 * d.n_lookups;
+    den = num + nz;
+    total = den + nz;
+  }
+};
+
 static Fp host_domain_omega(int k, bool inverse) {
   Fp root;
 #pragma unroll
@@ -921,6 +1120,19 @@ static int ppk_keygen(Ctx* c, PPk& pk, const uint8_t* desc, size_t desc_len) {
     int slots = 1 + d.n_advice + nchunks + 3 * d.n_lookups + 3;
     if (!pdev_slots(c, pk.pd.coef, pk.pd.coef_slots, slots, n)) return TG_ERR_NOMEM;
   }
+  // the Lagrange pool, sized the same way; its per-key part is uploaded here
+  {
+    LagLayout L(d);
+    if (!pdev_slots(c, pk.pd.lag, pk.pd.lag_slots, L.total, n)) return TG_ERR_NOMEM;
+    auto up = [&](int slot, const std::vector<Fp>& v) {
+      hipMemcpyAsync(pk.pd.lag + (size_t)slot * n, v.data(), n * sizeof(Fp),
+                     hipMemcpyHostToDevice, c->stream);
+    };
+    for (int j = 0; j < d.n_perm; j++) up(L.sigma + j, pk.sigma_lag[j]);
+    for (int col = 0; col < d.n_fixed; col++)
+      if (L.fixed_slot[col] >= 0) up(L.fixed_slot[col], d.fixed_lag[col]);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return TG_ERR_HIP;
+  }
   pk.ready = true;
   return 0;
 }
@@ -1108,9 +1320,20 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
 
   ts.common_scalar(pk.vk_repr);
 
+  // Lagrange pool slots (sized and half filled at keygen): every column is
+  // uploaded once, and the commits, the grand products and the transforms
+  // read it there
+  const LagLayout LG(d);
+  if (pd.lag_slots < LG.total) return TG_ERR_STATE;
+  auto lslot = [&](int idx) { return pd.lag + (size_t)idx * n; };
+  auto lag_up = [&](int idx, const std::vector<Fp>& v) {
+    hipMemcpyAsync(lslot(idx), v.data(), n * sizeof(Fp), hipMemcpyHostToDevice, c->stream);
+  };
+
   // 1. instance
   VestaAff inst_cm;
-  if (gpu_msm_commit(c, pd, inst_lag.data(), n, c->d_gl, one, c->h_w, inst_cm, &pk.wtab))
+  lag_up(LG.inst, inst_lag);
+  if (gpu_msm_commit_batch_dev(c, lslot(LG.inst), n, 1, c->d_gl, &one, &inst_cm, &pk.wtab))
     return TG_ERR_HIP;
   ts.common_point(inst_cm);
   st_.mark("instance_commit");
@@ -1127,8 +1350,8 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   auto cslot = [&](int idx) { return pd.coef + (size_t)idx * n; };
   Fp* d_inst_ext = pdev_ext_buf(pd, EB_INST);
   if (!d_inst_ext) return TG_ERR_NOMEM;
-  if (gpu_lag_to_coeff_ext_dev(c, pd, inst_lag.data(), cslot(CS_INST), d_inst_ext, d.k,
-                               d.ext_k, pk.n_inv, pk.zeta))
+  if (gpu_dlag_to_coeff_ext_dev(c, pd, lslot(LG.inst), cslot(CS_INST), d_inst_ext, d.k,
+                                d.ext_k, pk.n_inv, pk.zeta))
     return TG_ERR_HIP;
 
   // 2. advice
@@ -1137,13 +1360,10 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   std::vector<Fp> advice_blind(d.n_advice);
   for (int col = 0; col < d.n_advice; col++) advice_blind[col] = rng.field<FpCfg>();
   {
-    std::vector<Fp> cat((size_t)n * d.n_advice);
-    for (int col = 0; col < d.n_advice; col++)
-      memcpy(cat.data() + (size_t)col * n, advice_lag[col].data(),
-             (size_t)n * sizeof(Fp));
+    for (int col = 0; col < d.n_advice; col++) lag_up(LG.adv + col, advice_lag[col]);
     std::vector<VestaAff> cms(d.n_advice);
-    if (gpu_msm_commit_batch(c, pd, cat.data(), n, d.n_advice, c->d_gl,
-                             advice_blind.data(), cms.data(), &pk.wtab))
+    if (gpu_msm_commit_batch_dev(c, lslot(LG.adv), n, d.n_advice, c->d_gl,
+                                 advice_blind.data(), cms.data(), &pk.wtab))
       return TG_ERR_HIP;
     for (int col = 0; col < d.n_advice; col++)
       if (ts.write_point(cms[col])) return TG_ERR_BADARG;
@@ -1151,8 +1371,8 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   for (int col = 0; col < d.n_advice; col++) {
     Fp* dbuf = pdev_ext_buf(pd, EB_ADV + col);
     if (!dbuf) return TG_ERR_NOMEM;
-    if (gpu_lag_to_coeff_ext_dev(c, pd, advice_lag[col].data(), cslot(CS_ADV + col), dbuf,
-                                 d.k, d.ext_k, pk.n_inv, pk.zeta))
+    if (gpu_dlag_to_coeff_ext_dev(c, pd, lslot(LG.adv + col), cslot(CS_ADV + col), dbuf,
+                                  d.k, d.ext_k, pk.n_inv, pk.zeta))
       return TG_ERR_HIP;
   }
 
@@ -1220,12 +1440,15 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
       for (long i = u; i < n; i++) lkSp[l][i] = rng.field<FpCfg>();
       lkAp_blind[l] = rng.field<FpCfg>();
       lkSp_blind[l] = rng.field<FpCfg>();
-      std::vector<Fp> cat((size_t)n * 2);
-      memcpy(cat.data(), lkAp[l].data(), (size_t)n * sizeof(Fp));
-      memcpy(cat.data() + n, lkSp[l].data(), (size_t)n * sizeof(Fp));
+      // A', S' side by side for the commit; A, S for the grand product
+      lag_up(LG.lk + 4 * l, lkAp[l]);
+      lag_up(LG.lk + 4 * l + 1, lkSp[l]);
+      lag_up(LG.lk + 4 * l + 2, lkA[l]);
+      lag_up(LG.lk + 4 * l + 3, lkS[l]);
       Fp blds[2] = {lkAp_blind[l], lkSp_blind[l]};
       VestaAff cms[2];
-      if (gpu_msm_commit_batch(c, pd, cat.data(), n, 2, c->d_gl, blds, cms, &pk.wtab))
+      if (gpu_msm_commit_batch_dev(c, lslot(LG.lk + 4 * l), n, 2, c->d_gl, blds, cms,
+                                   &pk.wtab))
         return TG_ERR_HIP;
       if (ts.write_point(cms[0])) return TG_ERR_BADARG;
       if (ts.write_point(cms[1])) return TG_ERR_BADARG;
@@ -1238,85 +1461,71 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   // (finer marks inside the grand-product stage)
 
   // 4. permutation grand products (chunks CHAIN via last_z)
-  std::vector<std::vector<Fp>> permz_lag(nchunks);
-  std::vector<Fp> permz_blind(nchunks);
+  // on the device (grand_products.hip). z vector b < nchunks is chunk b's,
+  // the others are the lookups'; its rows 0..u come from the scan, rows
+  // u+1..n-1 are blinding drawn here, in the order the host loops drew them:
+  // per vector the rows, then the blind. The draws do not depend on the
+  // values, so nothing waits for the kernels.
+  const int nz = nchunks + nlk;
+  const long ntail = n - u - 1;
+  std::vector<Fp> z_tail((size_t)nz * ntail), z_blind(nz);  // outlive the next sync
+  auto draw_tail = [&](int b) {
+    Fp* t = z_tail.data() + (size_t)b * ntail;
+    for (long i = 0; i < ntail; i++) t[i] = rng.field<FpCfg>();
+    z_blind[b] = rng.field<FpCfg>();
+    if (ntail > 0)
+      hipMemcpyAsync(lslot(LG.z + b) + u + 1, t, ntail * sizeof(Fp), hipMemcpyHostToDevice,
+                     c->stream);
+  };
   {
-    std::vector<Fp> dpow(d.n_perm), wpow(n);
-    dpow[0] = fd_one_mont<FpCfg>();
-    for (int jj = 1; jj < d.n_perm; jj++) dpow[jj] = fd_mul(dpow[jj - 1], pk.delta);
-    wpow[0] = fd_one_mont<FpCfg>();
-    for (long i = 1; i < n; i++) wpow[i] = fd_mul(wpow[i - 1], pk.omega);
-    Fp last_z = fd_one_mont<FpCfg>();
-    for (int ch = 0; ch < nchunks; ch++) {
-      int lo = ch * d.chunk_len, hi = std::min(lo + d.chunk_len, d.n_perm);
-      std::vector<Fp> num(u), den(u);
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-      for (long i = 0; i < u; i++) {
-        Fp pn = fd_one_mont<FpCfg>(), pdv = fd_one_mont<FpCfg>();
-        for (int jj = lo; jj < hi; jj++) {
-          auto [kind, idx] = d.perm_cols[jj];
-          const Fp& v = kind == 0 ? advice_lag[idx][i]
-                        : kind == 1 ? d.fixed_lag[idx][i] : inst_lag[i];
-          pn = fd_mul(pn, fd_add(fd_add(fd_mul(beta, fd_mul(dpow[jj], wpow[i])), v), gamma));
-          pdv = fd_mul(pdv, fd_add(fd_add(fd_mul(beta, pk.sigma_lag[jj][i]), v), gamma));
-        }
-        num[i] = pn;
-        den[i] = pdv;
-      }
-      pbatch_inv(den.data(), u);
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-      for (long i = 0; i < u; i++) num[i] = fd_mul(num[i], den[i]);
-      permz_lag[ch].resize(n);
-      pprefix_prod(permz_lag[ch].data(), num.data(), u, last_z);
-      last_z = permz_lag[ch][u];
-      for (long i = u + 1; i < n; i++) permz_lag[ch][i] = rng.field<FpCfg>();
-      permz_blind[ch] = rng.field<FpCfg>();
+    std::vector<const Fp*> cols(d.n_perm), sigmas(d.n_perm);
+    for (int jj = 0; jj < d.n_perm; jj++) {
+      auto [kind, idx] = d.perm_cols[jj];
+      cols[jj] = lslot(kind == 0 ? LG.adv + (int)idx
+                       : kind == 1 ? LG.fixed_slot[idx] : LG.inst);
+      sigmas[jj] = lslot(LG.sigma + jj);
     }
+    int rc = dev_gp_perm_terms(c, pd, cols, sigmas, d.chunk_len, u, beta, gamma, pk.omega,
+                               pk.delta, lslot(LG.num), lslot(LG.den));
+    if (rc) return rc;
+    for (int ch = 0; ch < nchunks; ch++) draw_tail(ch);
   }
   st_.mark("gp_perm_z");
   /* perm z commits batched with lookup z below */
 
-  // 5. lookup grand products
-  std::vector<std::vector<Fp>> lkz_lag(nlk);
-  std::vector<Fp> lkz_blind(nlk);
-  for (int l = 0; l < nlk; l++) {
-    std::vector<Fp> den(u);
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-    for (long i = 0; i < u; i++)
-      den[i] = fd_mul(fd_add(lkAp[l][i], beta), fd_add(lkSp[l][i], gamma));
-    pbatch_inv(den.data(), u);
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-    for (long i = 0; i < u; i++)
-      den[i] = fd_mul(fd_mul(fd_add(lkA[l][i], beta), fd_add(lkS[l][i], gamma)), den[i]);
-    lkz_lag[l].resize(n);
-    pprefix_prod(lkz_lag[l].data(), den.data(), u, fd_one_mont<FpCfg>());
-    for (long i = u + 1; i < n; i++) lkz_lag[l][i] = rng.field<FpCfg>();
-    lkz_blind[l] = rng.field<FpCfg>();
+  // 5. lookup grand products; then ONE inversion over every chunk's and
+  // every lookup's denominators, and one scan: the chunks are one chain
+  // from 1 (each starts where the one before ended), every lookup its own
+  {
+    if (nlk > 0) {
+      const Fp *pa[TG_MAX_LOOKUPS], *psv[TG_MAX_LOOKUPS], *pap[TG_MAX_LOOKUPS],
+          *psp[TG_MAX_LOOKUPS];
+      for (int l = 0; l < nlk; l++) {
+        pap[l] = lslot(LG.lk + 4 * l);
+        psp[l] = lslot(LG.lk + 4 * l + 1);
+        pa[l] = lslot(LG.lk + 4 * l + 2);
+        psv[l] = lslot(LG.lk + 4 * l + 3);
+      }
+      int rc = dev_gp_lookup_terms(c, pd, nlk, pa, psv, pap, psp, u, beta, gamma,
+                                   lslot(LG.num) + (size_t)nchunks * u,
+                                   lslot(LG.den) + (size_t)nchunks * u);
+      if (rc) return rc;
+    }
+    int rc = dev_gp_batch_inverse(c, lslot(LG.den), (long)nz * u);
+    if (rc) return rc;
+    std::vector<GpSeg> segs(nz);
+    for (int b = 0; b < nz; b++)
+      segs[b] = GpSeg{u, lslot(LG.z + b), b > 0 && b < nchunks, one};
+    if ((rc = dev_gp_scan(c, pd, lslot(LG.num), lslot(LG.den), segs))) return rc;
+    for (int l = 0; l < nlk; l++) draw_tail(nchunks + l);
   }
   st_.mark("gp_lookup_z");
   {
-    int B = nchunks + nlk;
-    std::vector<Fp> cat((size_t)n * B), blinds(B);
+    int B = nz;
+    const std::vector<Fp>& blinds = z_blind;
     std::vector<VestaAff> cms(B);
-    for (int ch = 0; ch < nchunks; ch++) {
-      memcpy(cat.data() + (size_t)ch * n, permz_lag[ch].data(), (size_t)n * sizeof(Fp));
-      blinds[ch] = permz_blind[ch];
-    }
-    for (int l = 0; l < nlk; l++) {
-      memcpy(cat.data() + (size_t)(nchunks + l) * n, lkz_lag[l].data(),
-             (size_t)n * sizeof(Fp));
-      blinds[nchunks + l] = lkz_blind[l];
-    }
-    if (gpu_msm_commit_batch(c, pd, cat.data(), n, B, c->d_gl, blinds.data(), cms.data(),
-                             &pk.wtab))
+    if (gpu_msm_commit_batch_dev(c, lslot(LG.z), n, B, c->d_gl, blinds.data(), cms.data(),
+                                 &pk.wtab))
       return TG_ERR_HIP;
     for (int b = 0; b < B; b++)
       if (ts.write_point(cms[b])) return TG_ERR_BADARG;
@@ -1345,22 +1554,22 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   for (int ch = 0; ch < nchunks; ch++) {
     Fp* dbuf = pdev_ext_buf(pd, EB_PZ + ch);
     if (!dbuf) return TG_ERR_NOMEM;
-    if (gpu_lag_to_coeff_ext_dev(c, pd, permz_lag[ch].data(), cslot(CS_PZ + ch), dbuf, d.k,
-                                 d.ext_k, pk.n_inv, pk.zeta))
+    if (gpu_dlag_to_coeff_ext_dev(c, pd, lslot(LG.z + ch), cslot(CS_PZ + ch), dbuf, d.k,
+                                  d.ext_k, pk.n_inv, pk.zeta))
       return TG_ERR_HIP;
   }
   for (int l = 0; l < nlk; l++) {
     Fp *dz = pdev_ext_buf(pd, EB_LZ + l), *dap = pdev_ext_buf(pd, EB_AP + l),
        *dsp = pdev_ext_buf(pd, EB_SP + l);
     if (!dz || !dap || !dsp) return TG_ERR_NOMEM;
-    if (gpu_lag_to_coeff_ext_dev(c, pd, lkz_lag[l].data(), cslot(CS_LZ + l), dz, d.k,
-                                 d.ext_k, pk.n_inv, pk.zeta))
+    if (gpu_dlag_to_coeff_ext_dev(c, pd, lslot(LG.z + nchunks + l), cslot(CS_LZ + l), dz,
+                                  d.k, d.ext_k, pk.n_inv, pk.zeta))
       return TG_ERR_HIP;
-    if (gpu_lag_to_coeff_ext_dev(c, pd, lkAp[l].data(), cslot(CS_AP + l), dap, d.k, d.ext_k,
-                                 pk.n_inv, pk.zeta))
+    if (gpu_dlag_to_coeff_ext_dev(c, pd, lslot(LG.lk + 4 * l), cslot(CS_AP + l), dap, d.k,
+                                  d.ext_k, pk.n_inv, pk.zeta))
       return TG_ERR_HIP;
-    if (gpu_lag_to_coeff_ext_dev(c, pd, lkSp[l].data(), cslot(CS_SP + l), dsp, d.k, d.ext_k,
-                                 pk.n_inv, pk.zeta))
+    if (gpu_dlag_to_coeff_ext_dev(c, pd, lslot(LG.lk + 4 * l + 1), cslot(CS_SP + l), dsp,
+                                  d.k, d.ext_k, pk.n_inv, pk.zeta))
       return TG_ERR_HIP;
   }
   st_.mark("z_transforms");
@@ -1557,10 +1766,10 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
     pid_adv[col] = add_poly(cslot(CS_ADV + col), advice_blind[col]);
   std::vector<int> pid_pz(nchunks);
   for (int ch = 0; ch < nchunks; ch++)
-    pid_pz[ch] = add_poly(cslot(CS_PZ + ch), permz_blind[ch]);
+    pid_pz[ch] = add_poly(cslot(CS_PZ + ch), z_blind[ch]);
   std::vector<int> pid_lz(nlk), pid_lap(nlk), pid_lsp(nlk);
   for (int l = 0; l < nlk; l++) {
-    pid_lz[l] = add_poly(cslot(CS_LZ + l), lkz_blind[l]);
+    pid_lz[l] = add_poly(cslot(CS_LZ + l), z_blind[nchunks + l]);
     pid_lap[l] = add_poly(cslot(CS_AP + l), lkAp_blind[l]);
     pid_lsp[l] = add_poly(cslot(CS_SP + l), lkSp_blind[l]);
   }

@@ -21,6 +21,7 @@
 #include "msm.hip"
 #include "ntt.hip"
 #include "openings.hip"
+#include "grand_products.hip"
 #include "poseidon.hip"
 #include "binding_sig.hpp"
 #include "tx_wire.hpp"
@@ -118,7 +119,7 @@ struct ProfCounter {
 static const char* const PROF_NAMES[] = {
     "msm_digits", "msm_scan",  "msm_scatter", "msm_bucket_acc", "msm_reduce",
     "msm_wsum",   "ntt_stage", "ntt_fused",   "ntt_bitrev",     "ntt_scale",
-    "msm_total",  "ntt_total"};
+    "msm_total",  "ntt_total", "gp_terms",    "gp_inverse",     "gp_scan"};
 constexpr int PROF_N = sizeof(PROF_NAMES) / sizeof(PROF_NAMES[0]);
 
 struct PPk;
@@ -202,8 +203,9 @@ struct ProfScope {
 enum {
   P_MSM_DIGITS = 0, P_MSM_SCAN, P_MSM_SCATTER, P_MSM_ACC, P_MSM_REDUCE,
   P_MSM_WSUM, P_NTT_STAGE, P_NTT_FUSED, P_NTT_BITREV, P_NTT_SCALE,
-  P_MSM_TOTAL, P_NTT_TOTAL,
+  P_MSM_TOTAL, P_NTT_TOTAL, P_GP_TERMS, P_GP_INVERSE, P_GP_SCAN,
 };
+static_assert(P_GP_SCAN + 1 == PROF_N, "PROF_NAMES and the P_* indices disagree");
 
 }  // namespace taiga
 
@@ -1550,6 +1552,141 @@ int tg_ipa_open_probe(tg_ctx* ctx, uint32_t k, const uint8_t* poly, const uint8_
   diag_from_mont({a_final}, a_out);
   diag_from_mont({blind_acc}, blind_out);
   return TG_OK;
+}
+
+// ---------- diagnostics: the grand-product kernels on caller data ----------
+
+// most elements one of these calls takes (512 MiB of field elements)
+static const size_t GP_DIAG_MAX = (size_t)1 << 24;
+
+// download count Montgomery elements from d and write them out canonical
+static int diag_download(Ctx* c, const Fp* d, size_t count, uint8_t* out,
+                         const char* where) {
+  std::vector<Fp> res(count);
+  hipMemcpyAsync(res.data(), d, count * sizeof(Fp), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return set_err(c, where, e);
+  diag_from_mont(res, out);
+  return TG_OK;
+}
+
+int tg_fp_batch_inverse(tg_ctx* ctx, uint8_t* vals, size_t n) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  if (!n || n > GP_DIAG_MAX) return TG_ERR_BADARG;
+  std::vector<Fp> h;
+  if (!diag_to_mont(vals, n, h)) return TG_ERR_ENCODING;
+  DevTmp<Fp> d;
+  hipError_t e = diag_upload(c, d, h);
+  if (e != hipSuccess) return set_err(c, "inverse upload", e);
+  int rc = dev_gp_batch_inverse(c, d.p, (long)n);
+  if (rc) return rc;
+  return diag_download(c, d.p, n, vals, "inverse");
+}
+
+int tg_fp_prefix_product(tg_ctx* ctx, const uint8_t* ratios, const uint64_t* seg_lens,
+                         size_t nseg, const uint8_t init[32], uint8_t* z_out) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  if (!nseg || nseg > GP_DIAG_MAX) return TG_ERR_BADARG;
+  size_t total = 0;
+  for (size_t s = 0; s < nseg; s++) {
+    if (!seg_lens[s] || seg_lens[s] > GP_DIAG_MAX - total) return TG_ERR_BADARG;
+    total += seg_lens[s];
+  }
+  std::vector<Fp> h, i0;
+  if (!diag_to_mont(ratios, total, h) || !diag_to_mont(init, 1, i0))
+    return TG_ERR_ENCODING;
+  DevTmp<Fp> d, d_z;
+  hipError_t e = diag_upload(c, d, h);
+  if (e == hipSuccess) e = d_z.alloc(total + nseg);
+  if (e != hipSuccess) return set_err(c, "prefix upload", e);
+  std::vector<GpSeg> segs(nseg);
+  size_t zo = 0;
+  for (size_t s = 0; s < nseg; s++) {
+    segs[s] = GpSeg{(long)seg_lens[s], d_z.p + zo, s > 0, i0[0]};
+    zo += seg_lens[s] + 1;
+  }
+  DiagDev dd;
+  int rc = dev_gp_scan(c, dd.pd, d.p, nullptr, segs);
+  if (rc) return rc;
+  return diag_download(c, d_z.p, total + nseg, z_out, "prefix");
+}
+
+int tg_perm_product_probe(tg_ctx* ctx, uint32_t k, uint64_t u, uint32_t ncols,
+                          uint32_t chunk_len, const uint8_t* values, const uint8_t* sigmas,
+                          const uint8_t beta[32], const uint8_t gamma[32], uint8_t* z_out) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  if (k < 4 || k > 15 || !ncols || ncols > (uint32_t)TG_MAX_PERM || !chunk_len)
+    return TG_ERR_BADARG;
+  size_t n = (size_t)1 << k;
+  if (u < 1 || u >= n) return TG_ERR_BADARG;
+  uint32_t nchunks = (ncols + chunk_len - 1) / chunk_len;
+  if (nchunks > (uint32_t)TG_MAX_CHUNKS) return TG_ERR_BADARG;
+  std::vector<Fp> hv, hs, bg, gm;
+  if (!diag_to_mont(values, ncols * n, hv) || !diag_to_mont(sigmas, ncols * n, hs) ||
+      !diag_to_mont(beta, 1, bg) || !diag_to_mont(gamma, 1, gm))
+    return TG_ERR_ENCODING;
+  DevTmp<Fp> d_v, d_s, d_num, d_den, d_z;
+  hipError_t e = diag_upload(c, d_v, hv);
+  if (e == hipSuccess) e = diag_upload(c, d_s, hs);
+  if (e == hipSuccess) e = d_num.alloc(nchunks * u);
+  if (e == hipSuccess) e = d_den.alloc(nchunks * u);
+  if (e == hipSuccess) e = d_z.alloc(nchunks * (u + 1));
+  if (e != hipSuccess) return set_err(c, "perm probe upload", e);
+  // omega and delta as keygen derives them
+  Fp omega = host_domain_omega((int)k, false);
+  Fp delta{{5, 0, 0, 0}};
+  delta = fd_to_mont(delta);
+  for (int i = 0; i < 32; i++) delta = fd_sqr(delta);
+  std::vector<const Fp*> cols(ncols), sig(ncols);
+  for (uint32_t j = 0; j < ncols; j++) {
+    cols[j] = d_v.p + j * n;
+    sig[j] = d_s.p + j * n;
+  }
+  DiagDev dd;
+  int rc = dev_gp_perm_terms(c, dd.pd, cols, sig, (int)chunk_len, (long)u, bg[0], gm[0],
+                             omega, delta, d_num.p, d_den.p);
+  if (!rc) rc = dev_gp_batch_inverse(c, d_den.p, (long)(nchunks * u));
+  if (rc) return rc;
+  std::vector<GpSeg> segs(nchunks);
+  for (uint32_t ch = 0; ch < nchunks; ch++)
+    segs[ch] = GpSeg{(long)u, d_z.p + ch * (u + 1), ch > 0, fd_one_mont<FpCfg>()};
+  if ((rc = dev_gp_scan(c, dd.pd, d_num.p, d_den.p, segs))) return rc;
+  return diag_download(c, d_z.p, nchunks * (u + 1), z_out, "perm probe");
+}
+
+int tg_lookup_product_probe(tg_ctx* ctx, uint32_t k, uint64_t u, const uint8_t* a,
+                            const uint8_t* s, const uint8_t* ap, const uint8_t* sp,
+                            const uint8_t beta[32], const uint8_t gamma[32],
+                            uint8_t* z_out) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  if (k < 4 || k > 15) return TG_ERR_BADARG;
+  size_t n = (size_t)1 << k;
+  if (u < 1 || u >= n) return TG_ERR_BADARG;
+  std::vector<Fp> h[4], bg, gm;
+  const uint8_t* src[4] = {a, s, ap, sp};
+  for (int v = 0; v < 4; v++)
+    if (!diag_to_mont(src[v], n, h[v])) return TG_ERR_ENCODING;
+  if (!diag_to_mont(beta, 1, bg) || !diag_to_mont(gamma, 1, gm)) return TG_ERR_ENCODING;
+  DevTmp<Fp> d_in[4], d_num, d_den, d_z;
+  hipError_t e = hipSuccess;
+  for (int v = 0; v < 4 && e == hipSuccess; v++) e = diag_upload(c, d_in[v], h[v]);
+  if (e == hipSuccess) e = d_num.alloc(u);
+  if (e == hipSuccess) e = d_den.alloc(u);
+  if (e == hipSuccess) e = d_z.alloc(u + 1);
+  if (e != hipSuccess) return set_err(c, "lookup probe upload", e);
+  const Fp *pa = d_in[0].p, *ps = d_in[1].p, *pap = d_in[2].p, *psp = d_in[3].p;
+  DiagDev dd;
+  int rc = dev_gp_lookup_terms(c, dd.pd, 1, &pa, &ps, &pap, &psp, (long)u, bg[0], gm[0],
+                               d_num.p, d_den.p);
+  if (!rc) rc = dev_gp_batch_inverse(c, d_den.p, (long)u);
+  if (rc) return rc;
+  std::vector<GpSeg> segs{GpSeg{(long)u, d_z.p, false, fd_one_mont<FpCfg>()}};
+  if ((rc = dev_gp_scan(c, dd.pd, d_num.p, d_den.p, segs))) return rc;
+  return diag_download(c, d_z.p, u + 1, z_out, "lookup probe");
 }
 
 }  /* extern "C" */
