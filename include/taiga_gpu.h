@@ -74,10 +74,43 @@ int tg_load_srs(tg_ctx* ctx, const uint8_t* params_bytes, size_t len);
 int tg_srs_k(const tg_ctx* ctx); /* k, or TG_ERR_NOSRS */
 
 /* ---- variable-base MSM over Vesta (microbench entry) ----
- * base_set: 0 = custom bases (tg_bases_upload), 1 = SRS g,
- *           2 = SRS g_lagrange.
- * scalars: n x 32B canonical (vesta::Scalar = pallas::Base = Fp).
- * out_xy: 64B canonical affine result. */
+ * base_set: 0 = custom bases (tg_bases_upload / tg_gen_bases), 1 = SRS g,
+ *           2 = SRS g_lagrange. Any other value is TG_ERR_BADARG.
+ * scalars: n x 32B canonical (vesta::Scalar = pallas::Base = Fp). A scalar
+ *   >= p is TG_ERR_ENCODING, as for every other field input: the window
+ *   recoding covers 255 bits and is exact only below p.
+ * out_xy: 64B canonical affine result.
+ * n = 0 is TG_ERR_BADARG in every call of this section.
+ *
+ * Resident inputs. A context holds at most one custom base set and one
+ * scalar vector, each with a count of valid elements:
+ *   - tg_bases_upload, tg_gen_bases and tg_scalars_upload (and the upload
+ *     inside tg_msm_pallas) REPLACE what the context held. When one of them
+ *     fails, on a rejected value (TG_ERR_ENCODING) or on a HIP error, the
+ *     context afterwards holds NO input of that kind, not the old one and not
+ *     a partly converted new one.
+ *   - An MSM of n points needs n <= the resident count: tg_msm_resident
+ *     answers TG_ERR_STATE when fewer than n scalars are resident, and both
+ *     MSM calls answer TG_ERR_STATE over base_set 0 when fewer than n custom
+ *     bases are. Over the SRS sets they answer TG_ERR_NOSRS without an SRS
+ *     and TG_ERR_BADARG for n > 2^k. A prefix (n below the count) is fine.
+ *   - tg_bases_download answers TG_ERR_BADARG for n above the base count,
+ *     so also when no base set is resident.
+ *   - The scalar buffer is also the prover's: every call that proves,
+ *     verifies or generates a key (tg_keygen, tg_create_proof*, tg_*_prove,
+ *     tg_verify*, tg_ptx_*, tg_tx_verify*, tg_ipa_open_probe) overwrites it.
+ *     After one of them tg_msm_resident answers TG_ERR_STATE until the next
+ *     tg_scalars_upload. Custom bases and the resident polynomial are not
+ *     touched by those calls.
+ *   - Checks come in this order, all before any allocation or launch:
+ *     arguments (TG_ERR_BADARG), the base set (TG_ERR_NOSRS / TG_ERR_BADARG /
+ *     TG_ERR_STATE), then the scalars (TG_ERR_STATE, or the upload's own
+ *     result in tg_msm_pallas). A refused MSM call changes no resident input,
+ *     except that tg_msm_pallas, once it has begun its upload, replaces the
+ *     scalars as tg_scalars_upload does.
+ * Uploaded bases may hold the identity and equal points; MSMs over them take
+ * the accumulation path that handles those. Each upload or generation sets
+ * the path anew. */
 int tg_bases_upload(tg_ctx* ctx, const uint8_t* points_xy, size_t n);
 /* synthetic distinct bases generated on-device for benches: base i is
  * [k_i]G with k_i a 256-bit scalar derived from (seed, i) by splitmix64 —
@@ -91,17 +124,32 @@ int tg_msm_pallas(tg_ctx* ctx, const uint8_t* scalars, size_t n, int base_set,
                   uint8_t out_xy[64]);
 
 /* resident-input variant for measurement: scalars staged ahead of the timed
- * region (bench.py's contract: inputs already in HBM when timing starts). */
+ * region (bench.py's contract: inputs already in HBM when timing starts).
+ * The range check of the scalars is part of the upload; tg_msm_resident
+ * itself only compares counts. */
 int tg_scalars_upload(tg_ctx* ctx, const uint8_t* scalars, size_t n);
 int tg_msm_resident(tg_ctx* ctx, size_t n, int base_set, uint8_t out_xy[64]);
 
 /* ---- radix-2 NTT over Fp (microbench entry) ----
  * dir: 0 forward, 1 inverse (inverse includes the n^{-1} scaling).
- * coset: 0 plain domain (coset variants arrive with the prover pipeline).
- * poly: in-place 2^k x 32B canonical. */
+ * coset: 0 plain domain (coset variants arrive with the prover pipeline);
+ *   any other value is TG_ERR_BADARG.
+ * poly: in-place 2^k x 32B canonical; an element >= p is TG_ERR_ENCODING.
+ * k: 0..28. A larger k is TG_ERR_BADARG in every call of this section, and
+ *   is tested first, as the unsigned value it is, before anything is sized
+ *   from it. */
 int tg_ntt_fp(tg_ctx* ctx, int dir, uint32_t k, int coset, uint8_t* poly);
 
-/* resident-input variant: upload once, run on device data, download. */
+/* resident-input variant: upload once, run on device data, download.
+ * A context holds at most one resident polynomial, of one size:
+ *   - tg_poly_upload (and the upload inside tg_ntt_fp) REPLACES it. When the
+ *     upload fails, on an element >= p (TG_ERR_ENCODING) or on a HIP error,
+ *     the context afterwards holds NO polynomial, of the new size or the old.
+ *   - tg_ntt_resident transforms it in place and tg_poly_download copies it
+ *     out, leaving it as it is; both answer TG_ERR_STATE unless a polynomial
+ *     of exactly 2^k elements is resident. Bad arguments (k, coset) are
+ *     reported before missing state, and a refused call leaves the resident
+ *     data unchanged. */
 int tg_poly_upload(tg_ctx* ctx, const uint8_t* poly, uint32_t k);
 int tg_ntt_resident(tg_ctx* ctx, int dir, uint32_t k, int coset);
 int tg_poly_download(tg_ctx* ctx, uint8_t* poly, uint32_t k);

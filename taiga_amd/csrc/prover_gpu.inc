@@ -177,19 +177,26 @@ static int gpu_dlag_to_coeff_ext_dev(Ctx* c, ProverDev& pd, const Fp* d_lag,
                                   zeta, hipMemcpyDeviceToDevice);
 }
 
-// workspace and the canonical-scalar array for B MSMs of nn points each
+// workspace and the canonical-scalar array for B MSMs of nn points each.
+// The array is the buffer tg_scalars_upload fills: the prover is about to
+// overwrite it, so from here on it holds no caller scalars (tg_msm_resident
+// answers TG_ERR_STATE until the next tg_scalars_upload).
 static int gpu_msm_reserve(Ctx* c, long nn, int B) {
   long ntot = nn * B;
+  c->n_scalars = 0;
   if (msm_work_alloc(c->msm, (u64)ntot, (u64)B) != hipSuccess) return TG_ERR_NOMEM;
-  if (!c->d_scalars || c->n_scalars < (u64)ntot) {
+  if (!c->d_scalars || c->cap_scalars < (u64)ntot) {
     if (c->d_scalars) {
       hipStreamSynchronize(c->stream);
       hipFree(c->d_scalars);
       c->d_scalars = nullptr;
     }
-    if (hipMalloc(&c->d_scalars, ntot * sizeof(ScalarRepr)) != hipSuccess)
+    c->cap_scalars = 0;
+    if (hipMalloc(&c->d_scalars, ntot * sizeof(ScalarRepr)) != hipSuccess) {
+      c->d_scalars = nullptr;
       return TG_ERR_NOMEM;
-    c->n_scalars = (u64)ntot;
+    }
+    c->cap_scalars = (u64)ntot;
   }
   return 0;
 }

@@ -28,6 +28,7 @@
 #include "witness.hpp"
 #include "prover_impl.hpp"
 #include "hf_rtc.hpp"
+#include "resident_guard.hpp"
 
 namespace taiga {
 
@@ -42,6 +43,15 @@ __global__ void __launch_bounds__(256) k_to_mont_check(Fd<C>* out, const Fd<C>* 
     if (!fd_is_canonical(v)) atomicOr(err, 1u);
     out[i] = fd_to_mont(v);
   }
+}
+
+// canonicality check alone, for values that stay in canonical form (the MSM
+// scalars): read-only over in[0, n)
+template <class C>
+__global__ void __launch_bounds__(256) k_canonical_check(const Fd<C>* in, u64 n, unsigned* err) {
+  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n;
+       i += (u64)gridDim.x * blockDim.x)
+    if (!fd_is_canonical(in[i])) atomicOr(err, 1u);
 }
 
 template <class C>
@@ -135,14 +145,21 @@ struct Ctx {
   VestaAff* d_gl = nullptr;
   VestaAff h_w, h_u;  // Mont form, host copies
 
-  // custom bases / staged inputs
+  // custom bases / staged inputs. cap_* is what a buffer can hold; n_bases,
+  // n_scalars and poly_k say what valid caller input it holds now (0 / -1:
+  // none). They are cleared before a buffer is freed or overwritten and set
+  // again only when the new content is complete and accepted.
   VestaAff* d_bases = nullptr;
+  u64 cap_bases = 0;
   u64 n_bases = 0;
   bool bases_distinct = false;  // gen_bases output: distinct, non-identity
+  // shared with the prover (gpu_msm_reserve), which overwrites it
   ScalarRepr* d_scalars = nullptr;
+  u64 cap_scalars = 0;
   u64 n_scalars = 0;
   Fp* d_poly = nullptr;
   Fp* d_poly_tmp = nullptr;
+  u64 cap_poly = 0;  // elements in each of d_poly, d_poly_tmp
   int poly_k = -1;
 
   MsmWork msm;
@@ -227,6 +244,25 @@ struct DevTmp {
   }
   hipError_t alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)); }
 };
+
+// make a resident input buffer hold at least n elements (the entry points
+// leave no work pending on the stream, so the old buffer can go at once). The
+// caller has already cleared the count of valid elements; after a failed
+// allocation buf is null and cap is 0.
+template <class T>
+static hipError_t dev_reserve(T*& buf, u64& cap, u64 n) {
+  if (buf && cap >= n) return hipSuccess;
+  if (buf) hipFree(buf);
+  buf = nullptr;
+  cap = 0;
+  hipError_t e = hipMalloc(&buf, n * sizeof(T));
+  if (e != hipSuccess) {
+    buf = nullptr;
+    return e;
+  }
+  cap = n;
+  return hipSuccess;
+}
 
 // the 4-byte device flag the ingestion kernels OR their verdict into
 static hipError_t err_flag_new(DevTmp<unsigned>& f, hipStream_t stream) {
@@ -511,10 +547,11 @@ int tg_bases_upload(tg_ctx* ctx, const uint8_t* points_xy, size_t n) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
   if (!n) return TG_ERR_BADARG;
+  // from here on the old base set is replaced: a rejected upload leaves none
+  c->n_bases = 0;
+  c->bases_distinct = false;
   hipError_t e;
-  if (c->d_bases && c->n_bases < n) { hipFree(c->d_bases); c->d_bases = nullptr; }
-  if (!c->d_bases &&
-      (e = hipMalloc(&c->d_bases, n * sizeof(VestaAff))) != hipSuccess)
+  if ((e = dev_reserve(c->d_bases, c->cap_bases, n)) != hipSuccess)
     return set_err(c, "bases alloc", e);
   DevTmp<VestaAff> d_raw;
   DevTmp<unsigned> d_err;
@@ -530,7 +567,6 @@ int tg_bases_upload(tg_ctx* ctx, const uint8_t* points_xy, size_t n) {
   if (e != hipSuccess) return set_err(c, "bases upload", e);
   if (h_err) return TG_ERR_ENCODING;
   c->n_bases = n;
-  c->bases_distinct = false;
   return TG_OK;
 }
 
@@ -538,10 +574,10 @@ int tg_gen_bases(tg_ctx* ctx, size_t n, uint64_t seed) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
   if (!n) return TG_ERR_BADARG;
+  c->n_bases = 0;  // as in tg_bases_upload
+  c->bases_distinct = false;
   hipError_t e;
-  if (c->d_bases && c->n_bases < n) { hipFree(c->d_bases); c->d_bases = nullptr; }
-  if (!c->d_bases &&
-      (e = hipMalloc(&c->d_bases, n * sizeof(VestaAff))) != hipSuccess)
+  if ((e = dev_reserve(c->d_bases, c->cap_bases, n)) != hipSuccess)
     return set_err(c, "bases alloc", e);
   hipLaunchKernelGGL(k_gen_bases, dim3(msm_grid(n)), dim3(256), 0, c->stream, c->d_bases,
                      n, seed);
@@ -570,31 +606,53 @@ int tg_scalars_upload(tg_ctx* ctx, const uint8_t* scalars, size_t n) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
   if (!n) return TG_ERR_BADARG;
+  // from here on the old scalars are replaced: a rejected upload leaves none
+  c->n_scalars = 0;
   hipError_t e;
-  if (c->d_scalars && c->n_scalars < n) { hipFree(c->d_scalars); c->d_scalars = nullptr; }
-  if (!c->d_scalars &&
-      (e = hipMalloc(&c->d_scalars, n * sizeof(ScalarRepr))) != hipSuccess)
+  if ((e = dev_reserve(c->d_scalars, c->cap_scalars, n)) != hipSuccess)
     return set_err(c, "scalars alloc", e);
+  DevTmp<unsigned> d_err;
+  if ((e = err_flag_new(d_err, c->stream)) != hipSuccess)
+    return set_err(c, "scalars err alloc", e);
   hipMemcpyAsync(c->d_scalars, scalars, n * 32, hipMemcpyHostToDevice, c->stream);
+  // k_digits recodes 255 bits: a scalar >= p is refused here, once, so that
+  // tg_msm_resident need not look at the values again
+  hipLaunchKernelGGL(k_canonical_check<FpCfg>, dim3(msm_grid(n)), dim3(256), 0, c->stream,
+                     (const Fp*)c->d_scalars, (u64)n, d_err.p);
+  unsigned h_err = 0;
+  err_flag_read(d_err, &h_err, c->stream);
   e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return set_err(c, "scalars upload", e);
+  if (h_err) return TG_ERR_ENCODING;
   c->n_scalars = n;
   return TG_OK;
 }
 
-static int msm_common(Ctx* c, size_t n, int base_set, uint8_t out_xy[64]) {
-  // custom uploaded bases may contain identities/duplicates -> SAFE variant;
-  // SRS bases are distinct non-identity points -> fast branchless variant
-  const bool safe = base_set == 0 && !c->bases_distinct;
-  const VestaAff* bases = nullptr;
+// argument and base-set checks of an MSM of n points over base_set, before
+// any allocation or launch; on TG_OK *bases is the set and *safe says whether
+// it needs the accumulation that handles identities and equal x
+static int msm_guard(const Ctx* c, size_t n, int base_set, const VestaAff** bases,
+                     bool* safe) {
+  if (base_set < 0 || base_set > 2 || !n) return TG_ERR_BADARG;
   if (base_set == 0) {
-    if (c->n_bases < n) return TG_ERR_STATE;
-    bases = c->d_bases;
+    if (!c->d_bases || c->n_bases < n) return TG_ERR_STATE;
+    *bases = c->d_bases;
+    // custom uploaded bases may contain identities/duplicates -> SAFE variant
+    *safe = !c->bases_distinct;
   } else {
     if (c->k < 0) return TG_ERR_NOSRS;
     if (n > (1ULL << c->k)) return TG_ERR_BADARG;
-    bases = base_set == 1 ? c->d_g : c->d_gl;
+    *bases = base_set == 1 ? c->d_g : c->d_gl;
+    // SRS bases are distinct non-identity points -> fast branchless variant
+    *safe = false;
   }
+  return TG_OK;
+}
+
+// the MSM of the first n resident scalars (the caller has checked them) over
+// bases
+static int msm_common(Ctx* c, size_t n, const VestaAff* bases, bool safe,
+                      uint8_t out_xy[64]) {
   hipError_t e;
   if ((e = msm_work_alloc(c->msm, n)) != hipSuccess) return set_err(c, "msm ws", e);
   MsmCfg cfg = msm_cfg((long)n);
@@ -621,15 +679,24 @@ static int msm_common(Ctx* c, size_t n, int base_set, uint8_t out_xy[64]) {
 int tg_msm_resident(tg_ctx* ctx, size_t n, int base_set, uint8_t out_xy[64]) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
-  if (c->n_scalars < n) return TG_ERR_STATE;
-  return msm_common(c, n, base_set, out_xy);
+  const VestaAff* bases = nullptr;
+  bool safe = true;
+  int rc = msm_guard(c, n, base_set, &bases, &safe);
+  if (rc != TG_OK) return rc;
+  if (!c->d_scalars || c->n_scalars < n) return TG_ERR_STATE;
+  return msm_common(c, n, bases, safe, out_xy);
 }
 
 int tg_msm_pallas(tg_ctx* ctx, const uint8_t* scalars, size_t n, int base_set,
                   uint8_t out_xy[64]) {
-  int rc = tg_scalars_upload(ctx, scalars, n);
+  Ctx* c = (Ctx*)ctx;
+  if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  const VestaAff* bases = nullptr;
+  bool safe = true;
+  int rc = msm_guard(c, n, base_set, &bases, &safe);
   if (rc != TG_OK) return rc;
-  return msm_common((Ctx*)ctx, n, base_set, out_xy);
+  if ((rc = tg_scalars_upload(ctx, scalars, n)) != TG_OK) return rc;
+  return msm_common(c, n, bases, safe, out_xy);
 }
 
 // ---------- NTT ----------
@@ -637,17 +704,25 @@ int tg_msm_pallas(tg_ctx* ctx, const uint8_t* scalars, size_t n, int base_set,
 int tg_poly_upload(tg_ctx* ctx, const uint8_t* poly, uint32_t k) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
-  if (k > 28) return TG_ERR_BADARG;
-  u64 n = 1ULL << k;
+  u64 n;
+  int rc = ntt_size_guard(k, c->poly_k, false, &n);
+  if (rc != TG_OK) return rc;
+  // from here on the old polynomial is replaced: a rejected upload leaves none
+  c->poly_k = -1;
   hipError_t e;
-  if (c->poly_k != (int)k) {
+  if (c->cap_poly != n) {  // both buffers are exactly 2^k long
     if (c->d_poly) { hipFree(c->d_poly); c->d_poly = nullptr; }
     if (c->d_poly_tmp) { hipFree(c->d_poly_tmp); c->d_poly_tmp = nullptr; }
-    if ((e = hipMalloc(&c->d_poly, n * sizeof(Fp))) != hipSuccess)
+    c->cap_poly = 0;
+    if ((e = hipMalloc(&c->d_poly, n * sizeof(Fp))) != hipSuccess) {
+      c->d_poly = nullptr;
       return set_err(c, "poly alloc", e);
-    if ((e = hipMalloc(&c->d_poly_tmp, n * sizeof(Fp))) != hipSuccess)
+    }
+    if ((e = hipMalloc(&c->d_poly_tmp, n * sizeof(Fp))) != hipSuccess) {
+      c->d_poly_tmp = nullptr;
       return set_err(c, "poly tmp alloc", e);
-    c->poly_k = (int)k;
+    }
+    c->cap_poly = n;
   }
   DevTmp<unsigned> d_err;
   if ((e = err_flag_new(d_err, c->stream)) != hipSuccess)
@@ -661,21 +736,26 @@ int tg_poly_upload(tg_ctx* ctx, const uint8_t* poly, uint32_t k) {
   e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return set_err(c, "poly upload", e);
   if (h_err) return TG_ERR_ENCODING;
+  c->poly_k = (int)k;
   return TG_OK;
 }
 
 int tg_ntt_resident(tg_ctx* ctx, int dir, uint32_t k, int coset) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  u64 n;
+  int rc = ntt_size_guard(k, c->poly_k, true, &n);
+  // bad arguments are reported before missing state
+  if (rc == TG_ERR_BADARG) return rc;
   if (coset) return TG_ERR_BADARG;  // arrives with the prover pipeline
-  if (c->poly_k != (int)k) return TG_ERR_STATE;
+  if (rc != TG_OK) return rc;
   hipError_t e;
   if ((e = ntt_plan_init(c->ntt, (int)k, c->stream)) != hipSuccess)
     return set_err(c, "ntt plan", e);
   Fp ninv;
   if (dir) {
     // n^{-1} in Mont form, computed host-side with the shared primitives
-    Fp nstd{{1ULL << k, 0, 0, 0}};
+    Fp nstd{{n, 0, 0, 0}};
     ninv = fd_inv(fd_to_mont(nstd));
   }
   {
@@ -695,8 +775,9 @@ int tg_ntt_resident(tg_ctx* ctx, int dir, uint32_t k, int coset) {
 int tg_poly_download(tg_ctx* ctx, uint8_t* poly, uint32_t k) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
-  if (c->poly_k != (int)k) return TG_ERR_STATE;
-  u64 n = 1ULL << k;
+  u64 n;
+  int rc = ntt_size_guard(k, c->poly_k, true, &n);
+  if (rc != TG_OK) return rc;
   // from_mont into tmp, then D2H
   hipLaunchKernelGGL(k_from_mont<FpCfg>, dim3(ntt_grid(n)), dim3(256), 0, c->stream,
                      c->d_poly_tmp, c->d_poly, n);
