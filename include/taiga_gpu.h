@@ -68,8 +68,15 @@ const char* tg_error_string(const tg_ctx* ctx);
  * degenerate SRS: g or g_lagrange holding the identity or two points with the
  * same x coordinate (a repeat, or a point and its negation), or w or u being
  * the identity. MSMs over the SRS sets use an accumulation kernel without
- * identity / equal-x handling, and such an SRS commits to nothing. After a
- * rejected load the context holds no SRS (tg_srs_k gives TG_ERR_NOSRS). */
+ * identity / equal-x handling, and such an SRS commits to nothing.
+ * For k <= 17 the load also builds, per set, the fixed-base table that every
+ * MSM over that set then runs on: the window-shifted copies [2^(16*w)] G_j,
+ * w = 0..15 (16 x 2^k x 64 B per set and context: 2 x 32 MiB at k = 15). Any
+ * two points of a table can meet in one bucket, so the equal-x rule holds
+ * over each table as a whole: an SRS in which some [2^(16*w)] G_i and
+ * [2^(16*v)] G_j share an x coordinate (G_1 = [2^16] G_0, say) is
+ * TG_ERR_ENCODING too. After a rejected load the context holds no SRS and no
+ * table (tg_srs_k gives TG_ERR_NOSRS). */
 int tg_load_srs(tg_ctx* ctx, const uint8_t* params_bytes, size_t len);
 int tg_srs_k(const tg_ctx* ctx); /* k, or TG_ERR_NOSRS */
 

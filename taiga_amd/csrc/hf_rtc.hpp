@@ -46,15 +46,19 @@ inline std::string hf_rtc_prelude() {
   o << "typedef unsigned long long u64;\n"
        "typedef unsigned __int128 u128;\n"
        "struct Fp { u64 l[4]; };\n";
-  auto arr = [&](const char* name, const u64 v[4]) {
+  // the modulus as compile-time constants, as pasta_device.hpp has it: after
+  // unrolling, modv(i) folds, and the products with its zero limb and its
+  // 2^62 limb go away (a __constant__ array is opaque to the runtime compiler)
+  {
     char buf[256];
+    const u64* v = FpCfg::MOD;
     snprintf(buf, sizeof(buf),
-             "__device__ __constant__ u64 %s[4] = {%lluULL,%lluULL,%lluULL,%lluULL};\n",
-             name, (unsigned long long)v[0], (unsigned long long)v[1],
-             (unsigned long long)v[2], (unsigned long long)v[3]);
+             "__device__ __forceinline__ constexpr u64 modv(int i) {\n"
+             "  return i == 0 ? %lluULL : i == 1 ? %lluULL : i == 2 ? %lluULL : %lluULL;\n}\n",
+             (unsigned long long)v[0], (unsigned long long)v[1], (unsigned long long)v[2],
+             (unsigned long long)v[3]);
     o << buf;
-  };
-  arr("MODV", FpCfg::MOD);
+  }
   char buf[128];
   snprintf(buf, sizeof(buf), "#define FPINV 0x%llxULL\n",
            (unsigned long long)FpCfg::INV);
@@ -64,7 +68,7 @@ __device__ __forceinline__ void reduce_once(Fp& r) {
   u64 t[4]; u64 borrow = 0;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
-    u128 d = (u128)r.l[i] - MODV[i] - borrow;
+    u128 d = (u128)r.l[i] - modv(i) - borrow;
     t[i] = (u64)d; borrow = (u64)(d >> 64) ? 1 : 0;
   }
   if (!borrow) { r.l[0]=t[0]; r.l[1]=t[1]; r.l[2]=t[2]; r.l[3]=t[3]; }
@@ -89,7 +93,7 @@ __device__ __forceinline__ Fp f_sub(Fp a, Fp b) {
     u64 c = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      u128 s = (u128)r.l[i] + MODV[i] + c;
+      u128 s = (u128)r.l[i] + modv(i) + c;
       r.l[i] = (u64)s; c = (u64)(s >> 64);
     }
   }
@@ -101,7 +105,7 @@ __device__ __forceinline__ Fp f_neg(Fp a) {
   u64 borrow = 0; Fp r;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
-    u128 d = (u128)MODV[i] - a.l[i] - borrow;
+    u128 d = (u128)modv(i) - a.l[i] - borrow;
     r.l[i] = (u64)d; borrow = (u64)(d >> 64) ? 1 : 0;
   }
   return r;
@@ -117,10 +121,10 @@ __device__ __forceinline__ Fp f_mul(Fp a, Fp b) {
     s = (u128)a.l[3]*bi + t3 + carry; t3=(u64)s; carry=(u64)(s>>64);
     s = (u128)t4 + carry; t4=(u64)s; t5=(u64)(s>>64);
     u64 m = t0 * FPINV;
-    u128 c = (u128)m*MODV[0] + t0; carry=(u64)(c>>64);
-    c = (u128)m*MODV[1] + t1 + carry; t0=(u64)c; carry=(u64)(c>>64);
-    c = (u128)m*MODV[2] + t2 + carry; t1=(u64)c; carry=(u64)(c>>64);
-    c = (u128)m*MODV[3] + t3 + carry; t2=(u64)c; carry=(u64)(c>>64);
+    u128 c = (u128)m*modv(0) + t0; carry=(u64)(c>>64);
+    c = (u128)m*modv(1) + t1 + carry; t0=(u64)c; carry=(u64)(c>>64);
+    c = (u128)m*modv(2) + t2 + carry; t1=(u64)c; carry=(u64)(c>>64);
+    c = (u128)m*modv(3) + t3 + carry; t2=(u64)c; carry=(u64)(c>>64);
     c = (u128)t4 + carry; t3=(u64)c;
     t4 = t5 + (u64)(c>>64); t5 = 0;
   }

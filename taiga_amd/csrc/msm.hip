@@ -66,39 +66,50 @@ struct ScalarRepr {
   u64 l[4];
 };  // canonical LE
 
+// window w of the signed recoding of canonical s: sum_w d_w * 2^(c*w) = s
+// with |d_w| <= 2^(c-1). Returns the magnitude; sign and the carry into
+// window w+1 by reference (carry in: 0 for w = 0).
+TG_HD uint32_t msm_digit(const ScalarRepr& s, int w, int c, uint32_t& carry, uint32_t& sign) {
+  int bit0 = w * c;
+  int limb = bit0 >> 6, sh = bit0 & 63;
+  u64 raw = s.l[limb] >> sh;
+  if (sh && limb < 3 && sh + c > 64) raw |= s.l[limb + 1] << (64 - sh);
+  uint32_t d = ((uint32_t)raw & ((1u << c) - 1)) + carry;
+  sign = 0;
+  if (d > (1u << (c - 1))) {  // take d - 2^c, carry into the next window
+    d = (1u << c) - d;
+    sign = 1;
+    carry = 1;
+  } else {
+    carry = 0;
+  }
+  return d;
+}
+
 // digits: packed u32 = mag(17 bits) | sign<<17 ; mag==0 means skip.
-// hist[w * MSM_NBUCK + (mag-1)]++
+// hist[w * MSM_NBUCK + (mag-1)]++; with fixed set (the fixed-base chain,
+// msm_run_fixed) all windows of a batch element share ONE bucket set and the
+// histogram index has no window term: hist[mag-1]++
 __global__ void __launch_bounds__(256) k_digits(const ScalarRepr* sc, u64 n, u64 nn, MsmCfg cfg,
-                uint32_t* dig, uint32_t* hist) {
+                uint32_t* dig, uint32_t* hist, bool fixed) {
   // n = total scalars (= nn * batch); histogram is per batch b = i / nn
-  const u64 m = (u64)cfg.nwin * cfg.nbuck;
-  const uint32_t mask = (1u << cfg.c) - 1;
-  const uint32_t halfc = 1u << (cfg.c - 1);
+  const u64 m = fixed ? (u64)cfg.nbuck : (u64)cfg.nwin * cfg.nbuck;
+  const u64 wstride = fixed ? 0 : (u64)cfg.nbuck;
   for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n;
        i += (u64)gridDim.x * blockDim.x) {
     u64 bofs = (i / nn) * m;
     ScalarRepr s = sc[i];
     uint32_t carry = 0;
     for (int w = 0; w < cfg.nwin; w++) {
-      int bit0 = w * cfg.c;
-      int limb = bit0 >> 6, sh = bit0 & 63;
-      u64 raw = s.l[limb] >> sh;
-      if (sh && limb < 3 && sh + cfg.c > 64) raw |= s.l[limb + 1] << (64 - sh);
-      uint32_t d = ((uint32_t)raw & mask) + carry;
-      uint32_t sign = 0;
-      if (d > halfc) {  // take d - 2^c, carry into the next window
-        d = (1u << cfg.c) - d;
-        sign = 1;
-        carry = 1;
-      } else {
-        carry = 0;
-      }
+      uint32_t sign;
+      uint32_t d = msm_digit(s, w, cfg.c, carry, sign);
       uint32_t packed = d ? (d | (sign << 17)) : 0;
       dig[i * cfg.nwin + w] = packed;
-      if (d) atomicAdd(&hist[bofs + (u64)w * cfg.nbuck + (d - 1)], 1u);
+      if (d) atomicAdd(&hist[bofs + (u64)w * wstride + (d - 1)], 1u);
     }
     // the top window of a <2^255 scalar cannot carry out (its raw value +
-    // carry stays <= 2^(c-1) for c in {12,16})
+    // carry stays <= 2^(c-1) for c in {12,16}; msm_fb_nwin states the rule
+    // for any c)
   }
 }
 
@@ -187,10 +198,13 @@ inline void msm_scan(const uint32_t* in, uint32_t* out, uint32_t* bsum, u64 m,
                      out, bsum, m);
 }
 
-// scatter: sorted[off[bucket]++] = i | sign<<31
+// scatter: sorted[off[bucket]++] = i | sign<<31. With fb_stride = N != 0
+// (fixed-base chain) the one bucket set takes every window's digits and the
+// entry is the table index w * N + i, the point [2^(c*w)] G_i.
 __global__ void __launch_bounds__(256) k_scatter(const uint32_t* dig, u64 n, u64 nn, MsmCfg cfg,
-                 uint32_t* off, uint32_t* sorted) {
-  const u64 m = (u64)cfg.nwin * cfg.nbuck;
+                 uint32_t* off, uint32_t* sorted, uint32_t fb_stride) {
+  const u64 m = fb_stride ? (u64)cfg.nbuck : (u64)cfg.nwin * cfg.nbuck;
+  const u64 wstride = fb_stride ? 0 : (u64)cfg.nbuck;
   for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n;
        i += (u64)gridDim.x * blockDim.x) {
     u64 bofs = (i / nn) * m;
@@ -200,8 +214,8 @@ __global__ void __launch_bounds__(256) k_scatter(const uint32_t* dig, u64 n, u64
       uint32_t mag = packed & 0x1FFFFu;
       if (!mag) continue;
       uint32_t sign = (packed >> 17) & 1u;
-      uint32_t pos = atomicAdd(&off[bofs + (u64)w * cfg.nbuck + (mag - 1)], 1u);
-      sorted[pos] = il | (sign << 31);
+      uint32_t pos = atomicAdd(&off[bofs + (u64)w * wstride + (mag - 1)], 1u);
+      sorted[pos] = ((uint32_t)w * fb_stride + il) | (sign << 31);
     }
   }
 }
@@ -694,7 +708,7 @@ inline void msm_run(MsmWork& w, const ScalarRepr* d_scalars, u64 n, u64 nn, u64 
       [[maybe_unused]] auto p = prof(MSM_P_DIGITS);
       hipMemsetAsync(w.d_hist, 0, m * 4, stream);
       hipLaunchKernelGGL(k_digits, dim3(msm_grid(n)), dim3(256), 0, stream, d_scalars, n,
-                         nn, cfg, w.d_dig, w.d_hist);
+                         nn, cfg, w.d_dig, w.d_hist, false);
     }
     {
       [[maybe_unused]] auto p = prof(MSM_P_SCAN);
@@ -704,7 +718,7 @@ inline void msm_run(MsmWork& w, const ScalarRepr* d_scalars, u64 n, u64 nn, u64 
     {
       [[maybe_unused]] auto p = prof(MSM_P_SCATTER);
       hipLaunchKernelGGL(k_scatter, dim3(msm_grid(n)), dim3(256), 0, stream, w.d_dig, n,
-                         nn, cfg, w.d_off, w.d_sorted);
+                         nn, cfg, w.d_off, w.d_sorted, 0u);
       hipMemcpyAsync(w.d_end, w.d_off, m * 4, hipMemcpyDeviceToDevice, stream);
     }
     {
@@ -733,6 +747,192 @@ inline void msm_run(MsmWork& w, const ScalarRepr* d_scalars, u64 n, u64 nn, u64 
   }
   hipMemcpyAsync(wsums, w.d_wsums, sizeof(VestaJac) * cfg.nwin * B, hipMemcpyDeviceToHost,
                  stream);
+}
+
+// ---- fixed-base chain: window weights folded into a precomputed table ----
+// The SRS sets never change after tg_load_srs, so the weights 2^(c*w) that
+// the generic chain applies per MSM (nwin bucket reductions, then the host's
+// Horner combine) are applied to the bases once, at load:
+//   T[w][j] = [2^(c*w)] G_j,   sum_j k_j G_j = sum_j sum_w d_{j,w} T[w][j],
+// ONE bucket set per MSM, one reduction, one point back. Reduction cost no
+// longer grows with the window count, so the window is wider than msm_cfg's
+// c=13 at n=2^15 (profiles/README.md, round 6, has the measurements).
+constexpr int MSM_FB_C = 16;
+// windows by rule: the signed recoding carries out of the top window unless
+// that window's raw value stays below 2^(c-1). Scalars are canonical, so
+// < 2^255; with W = floor(255/c) + 1 windows c*W >= 256, the top window holds
+// at most 255 - c*(W-1) <= c - 1 bits, and raw + carry <= 2^(c-1) is not
+// recoded. ceil(255/c) windows fall one short exactly when c divides 255
+// (c = 15, 17): scalars in [2^254, p) then carry out of the top window.
+TG_HD constexpr int msm_fb_nwin(int c) { return 255 / c + 1; }
+constexpr int MSM_FB_NWIN = msm_fb_nwin(MSM_FB_C);
+constexpr int MSM_FB_NBUCK = 1 << (MSM_FB_C - 1);
+// tables are built for SRS sizes up to 2^MSM_FB_KMAX (64 B * nwin * 2^k per
+// set: 2 x 32 MiB at k=15); a larger SRS stays on the generic chain
+constexpr int MSM_FB_KMAX = 17;
+static_assert(MSM_FB_C <= MSM_C_MAX && MSM_FB_NWIN <= 32, "workspace sizing (msm_work_alloc)");
+static_assert((u64)MSM_FB_NWIN << MSM_FB_KMAX < (1ull << 31), "sorted entry: index | sign<<31");
+
+inline MsmCfg msm_fb_cfg() {
+  return MsmCfg{MSM_FB_C, MSM_FB_NWIN, MSM_FB_NBUCK, MSM_FB_NBUCK / MSM_SEG, MSM_SEG};
+}
+
+// table build, window w from window w-1: c doublings per point (Jacobian out)
+__global__ void __launch_bounds__(256) k_fb_dbl(const VestaAff* prev, VestaJac* out, u64 n, int c) {
+  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < n;
+       i += (u64)gridDim.x * blockDim.x) {
+    VestaJac p = jac_from_aff(prev[i]);
+    for (int b = 0; b < c; b++) p = jac_dbl(p);
+    out[i] = p;
+  }
+}
+
+// Jacobian -> Montgomery affine with a batched inversion: a thread walks
+// MSM_FB_INV_RUN consecutive points, inverts the product of their z once and
+// unwinds it. No point of the table is the identity (the group has prime
+// order and the SRS points are checked non-identity), so every z is nonzero.
+constexpr int MSM_FB_INV_RUN = 32;
+__global__ void __launch_bounds__(64) k_fb_to_aff(const VestaJac* in, VestaAff* out, u64 n) {
+  for (u64 t = blockIdx.x * (u64)blockDim.x + threadIdx.x; t * MSM_FB_INV_RUN < n;
+       t += (u64)gridDim.x * blockDim.x) {
+    const u64 i0 = t * MSM_FB_INV_RUN;
+    const int cnt = n - i0 < (u64)MSM_FB_INV_RUN ? (int)(n - i0) : MSM_FB_INV_RUN;
+    Fq pre[MSM_FB_INV_RUN];  // pre[i] = z_0 * ... * z_i
+    Fq acc = in[i0].z;
+    pre[0] = acc;
+    for (int i = 1; i < cnt; i++) {
+      acc = fd_mul(acc, in[i0 + i].z);
+      pre[i] = acc;
+    }
+    Fq inv = fd_inv(acc);  // 1 / (z_0 ... z_{cnt-1})
+    for (int i = cnt - 1; i >= 0; i--) {
+      VestaJac p = in[i0 + i];
+      Fq zi = i ? fd_mul(inv, pre[i - 1]) : inv;  // 1 / z_i
+      inv = fd_mul(inv, p.z);
+      Fq zi2 = fd_sqr(zi);
+      VestaAff a;
+      a.x = fd_mul(p.x, zi2);
+      a.y = fd_mul(p.y, fd_mul(zi2, zi));
+      out[i0 + i] = a;
+    }
+  }
+}
+
+// build tab[w * n + j] = [2^(MSM_FB_C * w)] bases[j], w < MSM_FB_NWIN; tmp
+// holds n Jacobian points
+inline void msm_fb_build(const VestaAff* bases, VestaAff* tab, VestaJac* tmp, u64 n,
+                         hipStream_t stream) {
+  hipMemcpyAsync(tab, bases, n * sizeof(VestaAff), hipMemcpyDeviceToDevice, stream);
+  const u64 runs = (n + MSM_FB_INV_RUN - 1) / MSM_FB_INV_RUN;
+  for (int w = 1; w < MSM_FB_NWIN; w++) {
+    hipLaunchKernelGGL(k_fb_dbl, dim3(msm_grid_(n)), dim3(256), 0, stream,
+                       tab + (u64)(w - 1) * n, tmp, n, MSM_FB_C);
+    hipLaunchKernelGGL(k_fb_to_aff, dim3(msm_grid_(runs, 64)), dim3(64), 0, stream, tmp,
+                       tab + (u64)w * n, n);
+  }
+}
+
+// the reduction at one window per batch element. The level-1 kernel is the
+// generic one; with a single bucket set per MSM there is parallelism to
+// spare, so segments are short (s = 4 against the generic 16 at this bucket
+// count) and a window has up to 32 chunks, which level 2 folds with 32 lanes
+// per term. Serial chain in point operations, c=16: 6 (segment) + 8 (chunk
+// tree) + 5 (chunk fold) + 14 (doublings) + 4 (terms) = 37, against 59 with
+// the generic c=16 row (s = 16, K = 8).
+constexpr int MSM_FB_SEG = 4;
+constexpr int MSM_FB_WS_KMAX = 32;
+constexpr int MSM_FB_K = MSM_FB_NBUCK / MSM_FB_SEG / MSM_WS_WIDTH;
+static_assert(MSM_FB_NBUCK / MSM_FB_SEG >= MSM_WS_WIDTH && MSM_FB_K <= MSM_FB_WS_KMAX &&
+                  MSM_FB_K <= MSM_NWIN_MAX * MSM_WS_KMAX,
+              "chunks per window: level-2 lanes and the d_partials allocation");
+static_assert(1 + 8 + 5 <= MSM_WS_TERMS, "level-2 terms: T, 8 planes, 5 chunk-index planes");
+
+// level 2, lane = KMAX*e + k of the wide form (msm_wsum_input with 32 chunks)
+TG_HD VestaJac msm_fb_wsum_input(const VestaJac* chunks, int Wd, int K, int lane) {
+  const int e = lane / MSM_FB_WS_KMAX, k = lane & (MSM_FB_WS_KMAX - 1);
+  const int lgw = msm_lg2(Wd), lgk = msm_lg2(K);
+  const VestaJac* c = chunks + k * MSM_CHUNK_OUT;
+  if (k >= K) return jac_identity<FqCfg>();
+  if (e == 0) return c[0];
+  if (e <= lgw) return c[1 + e];
+  int a = e - lgw - 1;
+  if (a < lgk && ((k >> a) & 1)) return c[1];
+  return jac_identity<FqCfg>();
+}
+
+// level 2, one block per batch element: K chunk results -> the MSM's sum
+__global__ void __launch_bounds__(MSM_WS_TERMS* MSM_FB_WS_KMAX) k_fb_window_sum(
+    const VestaJac* partials, VestaJac* wsums, int Wd, int K, int lgs) {
+  __shared__ VestaJac X[MSM_WS_TERMS * MSM_FB_WS_KMAX];
+  const int tid = threadIdx.x, k = tid & (MSM_FB_WS_KMAX - 1), e = tid / MSM_FB_WS_KMAX;
+  X[tid] = msm_fb_wsum_input(partials + (u64)blockIdx.x * K * MSM_CHUNK_OUT, Wd, K, tid);
+  __syncthreads();
+  for (int off = K / 2; off >= 1; off >>= 1) {
+    if (k < off) X[tid] = jac_add(X[tid], X[tid + off]);
+    __syncthreads();
+  }
+  VestaJac v = jac_identity<FqCfg>();
+  if (k == 0) v = msm_wsum_scale(X[tid], Wd, K, lgs, e);
+  __syncthreads();
+  if (k == 0) X[e] = v;
+  __syncthreads();
+  for (int off = MSM_WS_TERMS / 2; off >= 1; off >>= 1) {
+    if (tid < off) X[tid] = jac_add(X[tid], X[tid + off]);
+    __syncthreads();
+  }
+  if (tid == 0) wsums[blockIdx.x] = X[0];
+}
+
+// msm_run over a fixed-base table (msm_fb_build of an SRS set of N = tab_n
+// points): B MSMs over the first nn <= N bases. sums receives ONE Jacobian
+// point per MSM, the MSM itself: no host combine. The table's points must be
+// pairwise x-distinct (tg_load_srs checks it), for the branch-free
+// accumulation. w must be msm_work_alloc'ed for (n, B).
+template <class ProfFn>
+inline void msm_run_fixed(MsmWork& w, const ScalarRepr* d_scalars, u64 n, u64 nn, u64 B,
+                          const VestaAff* tab, u64 tab_n, hipStream_t stream, VestaJac* sums,
+                          ProfFn&& prof) {
+  const MsmCfg cfg = msm_fb_cfg();
+  const u64 m = (u64)cfg.nbuck * B;
+  {
+    [[maybe_unused]] auto chain = prof(MSM_P_CHAIN);
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_DIGITS);
+      hipMemsetAsync(w.d_hist, 0, m * 4, stream);
+      hipLaunchKernelGGL(k_digits, dim3(msm_grid(n)), dim3(256), 0, stream, d_scalars, n,
+                         nn, cfg, w.d_dig, w.d_hist, true);
+    }
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_SCAN);
+      msm_scan(w.d_hist, w.d_off, w.d_bsum, m, stream);
+      hipMemcpyAsync(w.d_hist, w.d_off, m * 4, hipMemcpyDeviceToDevice, stream);
+    }
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_SCATTER);
+      hipLaunchKernelGGL(k_scatter, dim3(msm_grid(n)), dim3(256), 0, stream, w.d_dig, n,
+                         nn, cfg, w.d_off, w.d_sorted, (uint32_t)tab_n);
+      hipMemcpyAsync(w.d_end, w.d_off, m * 4, hipMemcpyDeviceToDevice, stream);
+    }
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_ACC);
+      hipMemsetAsync(w.d_big + m, 0, 4, stream);
+      const uint32_t* ord = msm_len_sort(w, m, stream);
+      [[maybe_unused]] auto pk = prof(MSM_P_ACC_KERNELS);
+      msm_acc_launch<false>(w, m, tab, ord, stream);
+    }
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_REDUCE);
+      hipLaunchKernelGGL(k_bucket_segsum, dim3(B * MSM_FB_K), dim3(MSM_WS_WIDTH), 0, stream,
+                         w.d_buckets, w.d_partials, cfg.nbuck, MSM_FB_SEG);
+    }
+    {
+      [[maybe_unused]] auto p = prof(MSM_P_WSUM);
+      hipLaunchKernelGGL(k_fb_window_sum, dim3(B), dim3(MSM_WS_TERMS * MSM_FB_WS_KMAX), 0,
+                         stream, w.d_partials, w.d_wsums, MSM_WS_WIDTH, MSM_FB_K,
+                         msm_lg2(MSM_FB_SEG));
+    }
+  }
+  hipMemcpyAsync(sums, w.d_wsums, sizeof(VestaJac) * B, hipMemcpyDeviceToHost, stream);
 }
 
 // host-side final combine: acc = sum_w 2^(c*w) * wsum[w]  (Horner, ~240

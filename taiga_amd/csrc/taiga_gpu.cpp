@@ -143,6 +143,10 @@ struct Ctx {
   int k = -1;
   VestaAff* d_g = nullptr;
   VestaAff* d_gl = nullptr;
+  // fixed-base tables of d_g and d_gl (msm_fb_build): MSM_FB_NWIN arrays of
+  // 2^k points each, [2^(MSM_FB_C*w)] G_j. Null when k > MSM_FB_KMAX.
+  VestaAff* d_g_tab = nullptr;
+  VestaAff* d_gl_tab = nullptr;
   VestaAff h_w, h_u;  // Mont form, host copies
 
   // custom bases / staged inputs. cap_* is what a buffer can hold; n_bases,
@@ -408,7 +412,8 @@ void tg_destroy(tg_ctx* ctx) {
   c->ppk = nullptr;
 #define TGF(p) \
   if (p) hipFree(p)
-  TGF(c->d_g); TGF(c->d_gl); TGF(c->d_bases); TGF(c->d_scalars);
+  TGF(c->d_g); TGF(c->d_gl); TGF(c->d_g_tab); TGF(c->d_gl_tab);
+  TGF(c->d_bases); TGF(c->d_scalars);
   TGF(c->d_poly); TGF(c->d_poly_tmp);
   TGF(c->msm.d_dig); TGF(c->msm.d_hist); TGF(c->msm.d_off); TGF(c->msm.d_end);
   TGF(c->msm.d_bsum); TGF(c->msm.d_sorted); TGF(c->msm.d_buckets);
@@ -486,6 +491,48 @@ static bool srs_set_degenerate(const uint8_t* set, u64 cnt, bool check_dups) {
   return std::adjacent_find(enc.begin(), enc.end()) != enc.end();
 }
 
+// true when two of the cnt Montgomery-affine points share an x coordinate
+// (one sort, once per load; Montgomery form is a bijection, so equal x is
+// equal limbs)
+static bool aff_x_repeats(const VestaAff* pts, u64 cnt) {
+  std::vector<std::array<u64, 4>> xs(cnt);
+  for (u64 i = 0; i < cnt; i++) memcpy(xs[i].data(), pts[i].x.l, 32);
+  std::sort(xs.begin(), xs.end());
+  return std::adjacent_find(xs.begin(), xs.end()) != xs.end();
+}
+
+static void srs_free(Ctx* c) {
+  VestaAff** sets[4] = {&c->d_g, &c->d_gl, &c->d_g_tab, &c->d_gl_tab};
+  for (VestaAff** p : sets)
+    if (*p) { hipFree(*p); *p = nullptr; }
+}
+
+// the fixed-base tables of the two sets just decompressed. The branch-free
+// accumulation needs what srs_set_degenerate checks for a set to hold over a
+// whole table, since any two of its nwin * 2^k points can meet in a bucket
+// (G_1 = [2^c] G_0 passes the per-set check and would put T[1][0] = T[0][1]
+// into one bucket): a table with a repeated x is refused.
+static int srs_build_tables(Ctx* c, u64 n) {
+  hipError_t e;
+  const u64 tn = (u64)MSM_FB_NWIN * n;
+  if ((e = hipMalloc(&c->d_g_tab, tn * sizeof(VestaAff))) != hipSuccess)
+    return set_err(c, "srs alloc g table", e);
+  if ((e = hipMalloc(&c->d_gl_tab, tn * sizeof(VestaAff))) != hipSuccess)
+    return set_err(c, "srs alloc gl table", e);
+  DevTmp<VestaJac> d_tmp;
+  if ((e = d_tmp.alloc(n)) != hipSuccess) return set_err(c, "srs alloc table tmp", e);
+  msm_fb_build(c->d_g, c->d_g_tab, d_tmp.p, n, c->stream);
+  msm_fb_build(c->d_gl, c->d_gl_tab, d_tmp.p, n, c->stream);
+  std::vector<VestaAff> h_tab(tn);
+  for (const VestaAff* tab : {c->d_g_tab, c->d_gl_tab}) {
+    hipMemcpyAsync(h_tab.data(), tab, tn * sizeof(VestaAff), hipMemcpyDeviceToHost, c->stream);
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess)
+      return set_err(c, "srs table build", e);
+    if (aff_x_repeats(h_tab.data(), tn)) return TG_ERR_ENCODING;
+  }
+  return TG_OK;
+}
+
 int tg_load_srs(tg_ctx* ctx, const uint8_t* bytes, size_t len) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
@@ -502,8 +549,7 @@ int tg_load_srs(tg_ctx* ctx, const uint8_t* bytes, size_t len) {
       srs_set_degenerate(bytes + 4 + 64 * n, 2, false))
     return TG_ERR_ENCODING;
   hipError_t e;
-  if (c->d_g) { hipFree(c->d_g); c->d_g = nullptr; }
-  if (c->d_gl) { hipFree(c->d_gl); c->d_gl = nullptr; }
+  srs_free(c);
   if ((e = hipMalloc(&c->d_g, n * sizeof(VestaAff))) != hipSuccess)
     return set_err(c, "srs alloc g", e);
   if ((e = hipMalloc(&c->d_gl, n * sizeof(VestaAff))) != hipSuccess)
@@ -530,6 +576,13 @@ int tg_load_srs(tg_ctx* ctx, const uint8_t* bytes, size_t len) {
   e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return set_err(c, "srs decompress", e);
   if (h_err) return TG_ERR_ENCODING;
+  if (k <= (uint32_t)MSM_FB_KMAX) {
+    int rc = srs_build_tables(c, n);
+    if (rc != TG_OK) {
+      srs_free(c);  // a rejected load leaves no table (and no SRS) behind
+      return rc;
+    }
+  }
   c->h_w = h_wu[0];
   c->h_u = h_wu[1];
   c->k = (int)k;
@@ -632,7 +685,8 @@ int tg_scalars_upload(tg_ctx* ctx, const uint8_t* scalars, size_t n) {
 // any allocation or launch; on TG_OK *bases is the set and *safe says whether
 // it needs the accumulation that handles identities and equal x
 static int msm_guard(const Ctx* c, size_t n, int base_set, const VestaAff** bases,
-                     bool* safe) {
+                     bool* safe, const VestaAff** tab) {
+  *tab = nullptr;
   if (base_set < 0 || base_set > 2 || !n) return TG_ERR_BADARG;
   if (base_set == 0) {
     if (!c->d_bases || c->n_bases < n) return TG_ERR_STATE;
@@ -643,6 +697,7 @@ static int msm_guard(const Ctx* c, size_t n, int base_set, const VestaAff** base
     if (c->k < 0) return TG_ERR_NOSRS;
     if (n > (1ULL << c->k)) return TG_ERR_BADARG;
     *bases = base_set == 1 ? c->d_g : c->d_gl;
+    *tab = base_set == 1 ? c->d_g_tab : c->d_gl_tab;  // fixed-base chain if built
     // SRS bases are distinct non-identity points -> fast branchless variant
     *safe = false;
   }
@@ -650,9 +705,9 @@ static int msm_guard(const Ctx* c, size_t n, int base_set, const VestaAff** base
 }
 
 // the MSM of the first n resident scalars (the caller has checked them) over
-// bases
+// bases, by the fixed-base chain when tab is the set's table
 static int msm_common(Ctx* c, size_t n, const VestaAff* bases, bool safe,
-                      uint8_t out_xy[64]) {
+                      const VestaAff* tab, uint8_t out_xy[64]) {
   hipError_t e;
   if ((e = msm_work_alloc(c->msm, n)) != hipSuccess) return set_err(c, "msm ws", e);
   MsmCfg cfg = msm_cfg((long)n);
@@ -662,10 +717,13 @@ static int msm_common(Ctx* c, size_t n, const VestaAff* bases, bool safe,
                                       P_MSM_ACC,    P_MSM_REDUCE, P_MSM_WSUM,
                                       -1,           P_MSM_TOTAL};
   auto prof = [&](int idx) { return ProfScope(c, MSM_PROF_MAP[idx]); };
-  msm_run(c->msm, c->d_scalars, n, n, 1, bases, safe, c->stream, wsums, prof);
+  if (tab)
+    msm_run_fixed(c->msm, c->d_scalars, n, n, 1, tab, 1ULL << c->k, c->stream, wsums, prof);
+  else
+    msm_run(c->msm, c->d_scalars, n, n, 1, bases, safe, c->stream, wsums, prof);
   hipError_t es = hipStreamSynchronize(c->stream);
   if (es != hipSuccess) return set_err(c, "msm run", es);
-  VestaAff r = msm_host_combine(wsums, cfg);
+  VestaAff r = tab ? jac_to_aff(wsums[0]) : msm_host_combine(wsums, cfg);
   if (aff_is_identity(r)) {
     memset(out_xy, 0, 64);
   } else {
@@ -679,24 +737,24 @@ static int msm_common(Ctx* c, size_t n, const VestaAff* bases, bool safe,
 int tg_msm_resident(tg_ctx* ctx, size_t n, int base_set, uint8_t out_xy[64]) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
-  const VestaAff* bases = nullptr;
+  const VestaAff *bases = nullptr, *tab = nullptr;
   bool safe = true;
-  int rc = msm_guard(c, n, base_set, &bases, &safe);
+  int rc = msm_guard(c, n, base_set, &bases, &safe, &tab);
   if (rc != TG_OK) return rc;
   if (!c->d_scalars || c->n_scalars < n) return TG_ERR_STATE;
-  return msm_common(c, n, bases, safe, out_xy);
+  return msm_common(c, n, bases, safe, tab, out_xy);
 }
 
 int tg_msm_pallas(tg_ctx* ctx, const uint8_t* scalars, size_t n, int base_set,
                   uint8_t out_xy[64]) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
-  const VestaAff* bases = nullptr;
+  const VestaAff *bases = nullptr, *tab = nullptr;
   bool safe = true;
-  int rc = msm_guard(c, n, base_set, &bases, &safe);
+  int rc = msm_guard(c, n, base_set, &bases, &safe, &tab);
   if (rc != TG_OK) return rc;
   if ((rc = tg_scalars_upload(ctx, scalars, n)) != TG_OK) return rc;
-  return msm_common(c, n, bases, safe, out_xy);
+  return msm_common(c, n, bases, safe, tab, out_xy);
 }
 
 // ---------- NTT ----------

@@ -1,0 +1,90 @@
+"""CPU-side test of the signed-digit recoding the fixed-base MSM chain relies
+on (msm.hip: msm_digit at MSM_FB_C with msm_fb_nwin windows).
+
+tests/host/msm_fb_probe.cpp runs the function k_digits calls, on the host,
+for the edge scalars of msm_fb_cases.py and a few random ones. With one bucket
+set and no host combine nothing downstream can absorb a carry out of the top
+window, so for every canonical scalar: sum_w d_w * 2^(c*w) is the scalar
+itself (as an integer, not mod p), every |d_w| <= 2^(c-1), and no carry is
+left. Skips only when hipcc is absent."""
+import os
+import random
+import shutil
+import subprocess
+
+import pytest
+
+import pypasta as pp
+from conftest import REPO
+from msm_fb_cases import edge_scalars
+
+HIPCC = shutil.which("hipcc") or (
+    "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
+
+pytestmark = pytest.mark.skipif(HIPCC is None, reason="hipcc not installed")
+
+P = pp.P
+
+
+@pytest.fixture(scope="module")
+def probe_bin(tmp_path_factory):
+    out = tmp_path_factory.mktemp("msm_fb_probe") / "msm_fb_probe"
+    subprocess.run(
+        [HIPCC, "-O2", "-std=c++17", "--offload-arch=gfx950",
+         "-I", os.path.join(REPO, "taiga_amd", "csrc"),
+         os.path.join(REPO, "tests", "host", "msm_fb_probe.cpp"), "-o", str(out)],
+        check=True)
+    return str(out)
+
+
+@pytest.fixture(scope="module")
+def probe(probe_bin):
+    def run(scalars):
+        r = subprocess.run([probe_bin] + ["%064x" % s for s in scalars],
+                           capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, (r.returncode, r.stderr[-400:])
+        lines = r.stdout.split("\n")
+        c, nwin = map(int, lines[0][1:].split())
+        rows = [list(map(int, ln.split())) for ln in lines[1:] if ln]
+        assert len(rows) == len(scalars)
+        return c, nwin, rows
+
+    return run
+
+
+def test_window_count_rule(probe):
+    """floor(255/c) + 1 windows: one more than ceil(255/c) when c divides 255"""
+    c, nwin, _ = probe([])
+    assert nwin == 255 // c + 1
+    assert c * nwin >= 256  # the top window holds at most c-1 bits of a scalar < 2^255
+    assert (c, nwin) == (16, 16)  # the width the GPU tests are written for
+
+
+def test_recoding_is_exact(probe):
+    c, nwin, _ = probe([])
+    rng = random.Random(6000)
+    scal = edge_scalars(c, nwin) + [rng.randrange(P) for _ in range(32)]
+    assert {0, 1, P - 1, P - 2, 1 << 254, (1 << 254) - 1} <= set(scal)
+    _, _, rows = probe(scal)
+    carried = 0
+    for s, row in zip(scal, rows):
+        digits, carry = row[:-1], row[-1]
+        assert len(digits) == nwin
+        assert carry == 0, hex(s)
+        assert sum(d << (c * w) for w, d in enumerate(digits)) == s, hex(s)
+        assert all(abs(d) <= 1 << (c - 1) for d in digits), hex(s)
+        carried += sum(d < 0 for d in digits)
+    assert carried > nwin  # the list does exercise the recoding
+
+
+def test_fixed_base_reduction_matches_naive(probe_bin):
+    """the one-bucket-set reduction (segments of MSM_FB_SEG, up to 32 chunks
+    folded by k_fb_window_sum) against the suffix-sum walk on dense, empty and
+    all-equal bucket sets, and against one multiplication on single buckets"""
+    r = subprocess.run([probe_bin, "reduce"], capture_output=True, text=True, timeout=600)
+    rows = dict(ln.split() for ln in r.stdout.split("\n") if ln)
+    assert r.returncode == 0 and set(rows.values()) == {"OK"}, \
+        [k for k, v in rows.items() if v != "OK"]
+    assert {"random.b0", "random.b1", "allid.b0", "allequal.b0", "single.0.b0",
+            "single.32767.b0", "single.16384.b0", "single.1023.b0",
+            "single.1024.b0"} <= set(rows)
