@@ -14,8 +14,14 @@
 //                       affine points — the ceil(255/w)*n*68 B bytes model)
 //   5. k_bucket_segsum: per-segment running sums (tot, Y), reduced per
 //                       256-segment chunk to T, S and the bit planes of Y
-//   6. k_window_sum   : chunk results -> window sums (the host shim does
-//                       the double-and-add combine of the windows)
+//   6. k_window_sum   : chunk results -> one sum per bucket set
+//
+// There is one launch chain (msm_run) and two plans for it (MsmPlan). The
+// generic plan keeps a bucket set per window, so an MSM comes back as nwin
+// window sums and the host shim does the double-and-add combine. The
+// fixed-base plan gathers from a table of window-shifted SRS bases into ONE
+// bucket set: the MSM comes back as one point and there is nothing to
+// combine. msm_finish turns either answer into the MSM's Jacobian point.
 //
 // Scalars arrive in canonical (standard) form — digit extraction needs no
 // Montgomery conversion. Points live device-resident as Montgomery affine
@@ -41,6 +47,22 @@ constexpr int MSM_NWIN_MAX = 16;             // ceil(255/16) (alloc worst case
                                              // c=13 needs 20x4096 << 16x32768)
 constexpr int MSM_NBUCK_MAX = 1 << (MSM_C_MAX - 1);
 constexpr int MSM_SEG = 16;                  // seg len of the LARGE-c config
+// windows by rule: the signed recoding carries out of the top window unless
+// that window's raw value stays below 2^(c-1). Scalars are canonical, so
+// < 2^255; with W = floor(255/c) + 1 windows c*W >= 256, the top window holds
+// at most 255 - c*(W-1) <= c - 1 bits, and raw + carry <= 2^(c-1) is not
+// recoded. ceil(255/c) windows fall one short exactly when c divides 255
+// (c = 15, 17): scalars in [2^254, p) then carry out of the top window.
+TG_HD constexpr int msm_nwin(int c) { return 255 / c + 1; }
+// the widths msm_cfg answers; none divides 255, so for them the rule is
+// ceil(255/c) and the table the tests pin is where it was
+constexpr bool msm_c_generic(int c) { return (c >= 8 && c <= 13) || c == MSM_C_MAX; }
+constexpr bool msm_nwin_is_ceil() {
+  for (int c = 8; c <= MSM_C_MAX; c++)
+    if (msm_c_generic(c) && msm_nwin(c) != (255 + c - 1) / c) return false;
+  return true;
+}
+static_assert(msm_nwin_is_ceil(), "msm_cfg's window counts moved");
 struct MsmCfg {
   int c, nwin, nbuck, nseg, seg;  // the reduction picks its own segment
                                   // length (msm_red_seg); nseg/seg remain
@@ -48,7 +70,7 @@ struct MsmCfg {
 };
 inline MsmCfg msm_cfg(long n) {
   if (n >= (1L << 18))
-    return MsmCfg{16, 16, 1 << 15, (1 << 15) / MSM_SEG, MSM_SEG};
+    return MsmCfg{16, msm_nwin(16), 1 << 15, (1 << 15) / MSM_SEG, MSM_SEG};
   // below 2^18 the bucket space must track the MSM size (c ~ log2 n - 2,
   // floored at 8 to keep nwin <= 32 for the d_dig/d_wsums allocs): the prover's
   // n=2^15 commits and IPA rounds take c=13 (the rounds fold scalars over
@@ -59,7 +81,7 @@ inline MsmCfg msm_cfg(long n) {
   int sc = lg - 2 < 8 ? 8 : (lg - 2 > 13 ? 13 : lg - 2);
   int nbuck = 1 << (sc - 1);
   int sseg = nbuck / 1024 > 0 ? nbuck / 1024 : 1;
-  return MsmCfg{sc, (255 + sc - 1) / sc, nbuck, nbuck / sseg, sseg};
+  return MsmCfg{sc, msm_nwin(sc), nbuck, nbuck / sseg, sseg};
 }
 
 struct ScalarRepr {
@@ -87,8 +109,8 @@ TG_HD uint32_t msm_digit(const ScalarRepr& s, int w, int c, uint32_t& carry, uin
 }
 
 // digits: packed u32 = mag(17 bits) | sign<<17 ; mag==0 means skip.
-// hist[w * MSM_NBUCK + (mag-1)]++; with fixed set (the fixed-base chain,
-// msm_run_fixed) all windows of a batch element share ONE bucket set and the
+// hist[w * MSM_NBUCK + (mag-1)]++; with fixed set (the fixed-base plan of
+// msm_run) all windows of a batch element share ONE bucket set and the
 // histogram index has no window term: hist[mag-1]++
 __global__ void __launch_bounds__(256) k_digits(const ScalarRepr* sc, u64 n, u64 nn, MsmCfg cfg,
                 uint32_t* dig, uint32_t* hist, bool fixed) {
@@ -107,9 +129,8 @@ __global__ void __launch_bounds__(256) k_digits(const ScalarRepr* sc, u64 n, u64
       dig[i * cfg.nwin + w] = packed;
       if (d) atomicAdd(&hist[bofs + (u64)w * wstride + (d - 1)], 1u);
     }
-    // the top window of a <2^255 scalar cannot carry out (its raw value +
-    // carry stays <= 2^(c-1) for c in {12,16}; msm_fb_nwin states the rule
-    // for any c)
+    // the top window of a <2^255 scalar cannot carry out: cfg.nwin follows
+    // msm_nwin, which states the rule for any c
   }
 }
 
@@ -169,15 +190,15 @@ __global__ void __launch_bounds__(256) k_scan_add(uint32_t* out, const uint32_t*
   if (i < m) out[i] += bsum[i / 512];
 }
 
-// exclusive scan over m entries (two-level when m/512 exceeds one block's
-// LDS); bsum workspace holds level-1 (+ level-2) block sums.
-static inline int msm_grid_(u64 work, int block = 256) {
+static inline int msm_grid(u64 work, int block = 256) {
   u64 blocks = (work + block - 1) / block;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   return (int)blocks;
 }
 
+// exclusive scan over m entries (two-level when m/512 exceeds one block's
+// LDS); bsum workspace holds level-1 (+ level-2) block sums.
 inline void msm_scan(const uint32_t* in, uint32_t* out, uint32_t* bsum, u64 m,
                      hipStream_t stream) {
   u64 nb1 = (m + 511) / 512;
@@ -407,7 +428,7 @@ __global__ void __launch_bounds__(MSM_BIG_LANES, 1) k_bucket_acc_big(const uint3
 // P_b = sum_{t: bit b of t set} Y_t of the lane index t. The planes fall out
 // of ONE folding tree (msm_wtree_active): folding the upper half of the live
 // range onto the lower half leaves the upper half intact, and its plain sum is
-// the plane of that bit. Level 2 (k_window_sum, one block per window) adds
+// the plane of that bit. Level 2 (k_window_sum, one block per bucket set) adds
 // the K = M/Wd chunks up: with j = Wd*k + t,
 //   F = sum_b 2^b * sum_k P_{k,b} + Wd * sum_a 2^a * sum_{k: bit a set} S_k.
 // So every weight is applied by doublings once per window, never per segment.
@@ -417,7 +438,9 @@ __global__ void __launch_bounds__(MSM_BIG_LANES, 1) k_bucket_acc_big(const uint3
 
 // level-1 segment length, chosen per bucket-space size for depth against
 // parallelism (independent of MsmCfg::seg, which only the tests' table pins)
-TG_HD int msm_red_seg(int nbuck) { return nbuck <= 1024 ? 2 : (nbuck <= 4096 ? 4 : 16); }
+TG_HD constexpr int msm_red_seg(int nbuck) {
+  return nbuck <= 1024 ? 2 : (nbuck <= 4096 ? 4 : 16);
+}
 
 // level 1, one segment B[0..s): tot = sum (q+1)*B[q], y = sum B[q]
 TG_HD void msm_seg_sums(const VestaJac* B, int s, VestaJac& tot, VestaJac& y) {
@@ -432,12 +455,15 @@ TG_HD void msm_seg_sums(const VestaJac* B, int s, VestaJac& tot, VestaJac& y) {
 }
 
 constexpr int MSM_WS_WIDTH = 256;  // segments per chunk = lanes of a level-1 block
-constexpr int MSM_WS_KMAX = 8;     // chunks per window at most (c=16: 2048 segments)
+// level-2 lanes per term = chunks per bucket set at most, the two widths of
+// k_window_sum: 8 serves the generic plan (c=16: 2048 segments), 32 the fixed-base
+constexpr int MSM_WS_KMAX = 8;
+constexpr int MSM_WS_KWIDE = 32;
 constexpr int MSM_CHUNK_OUT = 10;  // points a chunk hands on: T, S, P_0..P_7
-constexpr int MSM_WS_TERMS = 16;   // level-2 sum: T, <= 8 planes, <= 3 chunk-index planes
+constexpr int MSM_WS_TERMS = 16;   // level-2 sum: T, <= 8 planes, <= 5 chunk-index planes
 
-TG_HD int msm_ws_width(int M) { return M < MSM_WS_WIDTH ? M : MSM_WS_WIDTH; }
-TG_HD int msm_lg2(int v) {
+TG_HD constexpr int msm_ws_width(int M) { return M < MSM_WS_WIDTH ? M : MSM_WS_WIDTH; }
+TG_HD constexpr int msm_lg2(int v) {
   int l = 0;
   while ((1 << l) < v) l++;
   return l;
@@ -480,11 +506,13 @@ TG_HD void msm_chunk_store(const VestaJac* C, const VestaJac* T, int Wd, u64 q, 
   partials[q * MSM_CHUNK_OUT + tid] = tid == 0 ? T[0] : (tid == 1 ? C[0] : C[1 << (tid - 2)]);
 }
 
-// level 2, lane = 8*e + k: chunk k's summand of term e of
+// level 2, lane = KMAX*e + k: chunk k's summand of term e of
 //   W = sum_k T_k + s * (sum_b 2^b * sum_k P_{k,b} + Wd * sum_a 2^a * sum_{k: bit a} S_k)
 // (e = 0: T; e = 1..lgw: plane e-1; e = lgw+1+a: chunk-index plane a)
+// KMAX = lanes per term; the narrow width unless named
+template <int KMAX = MSM_WS_KMAX>
 TG_HD VestaJac msm_wsum_input(const VestaJac* chunks, int Wd, int K, int lane) {
-  const int e = lane >> 3, k = lane & (MSM_WS_KMAX - 1);
+  const int e = lane / KMAX, k = lane & (KMAX - 1);
   const int lgw = msm_lg2(Wd), lgk = msm_lg2(K);
   const VestaJac* c = chunks + k * MSM_CHUNK_OUT;
   if (k >= K) return jac_identity<FqCfg>();
@@ -523,15 +551,17 @@ __global__ void __launch_bounds__(MSM_WS_WIDTH, 1) k_bucket_segsum(const VestaJa
   msm_chunk_store(C, T, Wd, blockIdx.x, tid, partials);
 }
 
-// level 2: block w turns window w's K chunk results into one Jacobian window
-// sum (the window sums go to the host shim, which does the O(1) Horner
-// combine with the same TG_HD primitives)
-__global__ void __launch_bounds__(MSM_WS_TERMS* MSM_WS_KMAX) k_window_sum(const VestaJac* partials,
-                                                                          VestaJac* wsums, int Wd,
-                                                                          int K, int lgs) {
-  __shared__ VestaJac X[MSM_WS_TERMS * MSM_WS_KMAX];
-  const int tid = threadIdx.x, k = tid & (MSM_WS_KMAX - 1), e = tid >> 3;
-  X[tid] = msm_wsum_input(partials + (u64)blockIdx.x * K * MSM_CHUNK_OUT, Wd, K, tid);
+// level 2: block w turns bucket set w's K <= KMAX chunk results into one
+// Jacobian sum, KMAX lanes per term (a window sum under the generic plan,
+// which the host shim combines with the same TG_HD primitives; the MSM itself
+// under the fixed-base plan)
+template <int KMAX>
+__global__ void __launch_bounds__(MSM_WS_TERMS* KMAX) k_window_sum(const VestaJac* partials,
+                                                                   VestaJac* wsums, int Wd, int K,
+                                                                   int lgs) {
+  __shared__ VestaJac X[MSM_WS_TERMS * KMAX];
+  const int tid = threadIdx.x, k = tid & (KMAX - 1), e = tid / KMAX;
+  X[tid] = msm_wsum_input<KMAX>(partials + (u64)blockIdx.x * K * MSM_CHUNK_OUT, Wd, K, tid);
   __syncthreads();
   for (int off = K / 2; off >= 1; off >>= 1) {
     if (k < off) X[tid] = jac_add(X[tid], X[tid + off]);
@@ -587,16 +617,17 @@ __global__ void __launch_bounds__(256) k_gen_bases(VestaAff* out, u64 n, u64 see
 }
 
 // ---- workspace + launcher ----
+// (sets = MsmPlan::sets(), bucket sets per MSM: nwin, or 1 with a table)
 struct MsmWork {
   uint32_t* d_dig = nullptr;     // n * NWIN
-  uint32_t* d_hist = nullptr;    // NWIN * NBUCK   (start offsets after scan)
+  uint32_t* d_hist = nullptr;    // sets * NBUCK per MSM (start offsets after scan)
   uint32_t* d_off = nullptr;     // running copy for scatter
   uint32_t* d_end = nullptr;     // end offsets (= start + count)
   uint32_t* d_bsum = nullptr;    // scan block sums
-  uint32_t* d_sorted = nullptr;  // n * NWIN entries
-  VestaJac* d_buckets = nullptr;
-  VestaJac* d_partials = nullptr;
-  VestaJac* d_wsums = nullptr;  // MSM_NWIN window sums (combined on host)
+  uint32_t* d_sorted = nullptr;  // n * NWIN entries (base or table indices)
+  VestaJac* d_buckets = nullptr;   // sets * NBUCK per MSM
+  VestaJac* d_partials = nullptr;  // sets * K chunks of MSM_CHUNK_OUT per MSM
+  VestaJac* d_wsums = nullptr;  // sets sums per MSM (msm_finish, on the host)
   uint32_t* d_big = nullptr;    // big-bucket work list + count (phase 2)
   uint32_t* d_order = nullptr;  // bucket ids counting-sorted by length
   uint32_t* d_lhist = nullptr;  // MSM_LEN_BINS length histogram / offsets
@@ -624,9 +655,10 @@ inline hipError_t msm_work_alloc(MsmWork& w, u64 n_total, u64 batch = 1) {
   if ((e = hipMalloc(&w.d_bsum, (nb1 + (nb1 + 511) / 512 + 1) * 4)) != hipSuccess) return e;
   if ((e = hipMalloc(&w.d_sorted, n_total * 32 * 4)) != hipSuccess) return e;
   if ((e = hipMalloc(&w.d_buckets, m * sizeof(VestaJac))) != hipSuccess) return e;
-  // MSM_CHUNK_OUT points per level-1 chunk, nwin * batch * K chunks. Worst
+  // MSM_CHUNK_OUT points per level-1 chunk, sets * batch * K chunks. Worst
   // case c=16: nwin * K = 16 * 8 = 128 per batch, exactly this; the other
-  // rows have 32, 29, 26 (K=1), 48, 44 (K=2) and 80 (c=13, K=4).
+  // rows have 32, 29, 26 (K=1), 48, 44 (K=2) and 80 (c=13, K=4), the
+  // fixed-base plan 1 * 32 (msm_plans_fit holds every plan to it).
   if ((e = hipMalloc(&w.d_partials, (u64)MSM_NWIN_MAX * MSM_WS_KMAX * batch * MSM_CHUNK_OUT *
                                         sizeof(VestaJac))) != hipSuccess)
     return e;
@@ -639,13 +671,6 @@ inline hipError_t msm_work_alloc(MsmWork& w, u64 n_total, u64 batch = 1) {
   w.cap_n = n_total;
   w.cap_b = batch;
   return hipSuccess;
-}
-
-static inline int msm_grid(u64 work, int block = 256) {
-  u64 blocks = (work + block - 1) / block;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
 }
 
 // counting-sort bucket ids by length into w.d_order (see MSM_LEN_BINS note);
@@ -690,92 +715,22 @@ enum {
 // the unprofiled ProfFn
 inline int msm_noprof(int) { return 0; }
 
-// B same-size MSMs (nn points each, n = nn * B canonical device scalars)
-// over ONE device base array: enqueues the whole kernel chain on stream and
-// the copy of the cfg.nwin * B Jacobian window sums to host wsums (valid
-// after the caller synchronizes the stream; combine each MSM's nwin sums
-// with msm_host_combine*). w must be msm_work_alloc'ed for (n, B).
-// ProfFn: callable int->RAII scope, as in ntt_run (msm_noprof for none).
-template <class ProfFn>
-inline void msm_run(MsmWork& w, const ScalarRepr* d_scalars, u64 n, u64 nn, u64 B,
-                    const VestaAff* bases, bool safe, hipStream_t stream,
-                    VestaJac* wsums, ProfFn&& prof) {
-  MsmCfg cfg = msm_cfg((long)nn);
-  u64 m = (u64)cfg.nwin * cfg.nbuck * B;
-  {
-    [[maybe_unused]] auto chain = prof(MSM_P_CHAIN);
-    {
-      [[maybe_unused]] auto p = prof(MSM_P_DIGITS);
-      hipMemsetAsync(w.d_hist, 0, m * 4, stream);
-      hipLaunchKernelGGL(k_digits, dim3(msm_grid(n)), dim3(256), 0, stream, d_scalars, n,
-                         nn, cfg, w.d_dig, w.d_hist, false);
-    }
-    {
-      [[maybe_unused]] auto p = prof(MSM_P_SCAN);
-      msm_scan(w.d_hist, w.d_off, w.d_bsum, m, stream);
-      hipMemcpyAsync(w.d_hist, w.d_off, m * 4, hipMemcpyDeviceToDevice, stream);
-    }
-    {
-      [[maybe_unused]] auto p = prof(MSM_P_SCATTER);
-      hipLaunchKernelGGL(k_scatter, dim3(msm_grid(n)), dim3(256), 0, stream, w.d_dig, n,
-                         nn, cfg, w.d_off, w.d_sorted, 0u);
-      hipMemcpyAsync(w.d_end, w.d_off, m * 4, hipMemcpyDeviceToDevice, stream);
-    }
-    {
-      [[maybe_unused]] auto p = prof(MSM_P_ACC);
-      hipMemsetAsync(w.d_big + m, 0, 4, stream);
-      const uint32_t* ord = msm_len_sort(w, m, stream);
-      [[maybe_unused]] auto pk = prof(MSM_P_ACC_KERNELS);
-      if (safe)
-        msm_acc_launch<true>(w, m, bases, ord, stream);
-      else
-        msm_acc_launch<false>(w, m, bases, ord, stream);
-    }
-    const int rseg = msm_red_seg(cfg.nbuck);
-    const int rWd = msm_ws_width(cfg.nbuck / rseg);  // segments per chunk
-    const int rK = cfg.nbuck / rseg / rWd;           // chunks per window
-    {
-      [[maybe_unused]] auto p = prof(MSM_P_REDUCE);
-      hipLaunchKernelGGL(k_bucket_segsum, dim3(cfg.nwin * B * rK), dim3(MSM_WS_WIDTH), 0,
-                         stream, w.d_buckets, w.d_partials, cfg.nbuck, rseg);
-    }
-    {
-      [[maybe_unused]] auto p = prof(MSM_P_WSUM);
-      hipLaunchKernelGGL(k_window_sum, dim3(cfg.nwin * B), dim3(MSM_WS_TERMS * MSM_WS_KMAX), 0,
-                         stream, w.d_partials, w.d_wsums, rWd, rK, msm_lg2(rseg));
-    }
-  }
-  hipMemcpyAsync(wsums, w.d_wsums, sizeof(VestaJac) * cfg.nwin * B, hipMemcpyDeviceToHost,
-                 stream);
-}
-
-// ---- fixed-base chain: window weights folded into a precomputed table ----
+// ---- fixed-base tables: window weights folded into precomputed bases ----
 // The SRS sets never change after tg_load_srs, so the weights 2^(c*w) that
-// the generic chain applies per MSM (nwin bucket reductions, then the host's
+// the generic plan applies per MSM (nwin bucket reductions, then the host's
 // Horner combine) are applied to the bases once, at load:
 //   T[w][j] = [2^(c*w)] G_j,   sum_j k_j G_j = sum_j sum_w d_{j,w} T[w][j],
 // ONE bucket set per MSM, one reduction, one point back. Reduction cost no
 // longer grows with the window count, so the window is wider than msm_cfg's
 // c=13 at n=2^15 (profiles/README.md, round 6, has the measurements).
 constexpr int MSM_FB_C = 16;
-// windows by rule: the signed recoding carries out of the top window unless
-// that window's raw value stays below 2^(c-1). Scalars are canonical, so
-// < 2^255; with W = floor(255/c) + 1 windows c*W >= 256, the top window holds
-// at most 255 - c*(W-1) <= c - 1 bits, and raw + carry <= 2^(c-1) is not
-// recoded. ceil(255/c) windows fall one short exactly when c divides 255
-// (c = 15, 17): scalars in [2^254, p) then carry out of the top window.
-TG_HD constexpr int msm_fb_nwin(int c) { return 255 / c + 1; }
-constexpr int MSM_FB_NWIN = msm_fb_nwin(MSM_FB_C);
+constexpr int MSM_FB_NWIN = msm_nwin(MSM_FB_C);
 constexpr int MSM_FB_NBUCK = 1 << (MSM_FB_C - 1);
 // tables are built for SRS sizes up to 2^MSM_FB_KMAX (64 B * nwin * 2^k per
-// set: 2 x 32 MiB at k=15); a larger SRS stays on the generic chain
+// set: 2 x 32 MiB at k=15); a larger SRS stays on the generic plan
 constexpr int MSM_FB_KMAX = 17;
 static_assert(MSM_FB_C <= MSM_C_MAX && MSM_FB_NWIN <= 32, "workspace sizing (msm_work_alloc)");
 static_assert((u64)MSM_FB_NWIN << MSM_FB_KMAX < (1ull << 31), "sorted entry: index | sign<<31");
-
-inline MsmCfg msm_fb_cfg() {
-  return MsmCfg{MSM_FB_C, MSM_FB_NWIN, MSM_FB_NBUCK, MSM_FB_NBUCK / MSM_SEG, MSM_SEG};
-}
 
 // table build, window w from window w-1: c doublings per point (Jacobian out)
 __global__ void __launch_bounds__(256) k_fb_dbl(const VestaAff* prev, VestaJac* out, u64 n, int c) {
@@ -825,82 +780,94 @@ inline void msm_fb_build(const VestaAff* bases, VestaAff* tab, VestaJac* tmp, u6
   hipMemcpyAsync(tab, bases, n * sizeof(VestaAff), hipMemcpyDeviceToDevice, stream);
   const u64 runs = (n + MSM_FB_INV_RUN - 1) / MSM_FB_INV_RUN;
   for (int w = 1; w < MSM_FB_NWIN; w++) {
-    hipLaunchKernelGGL(k_fb_dbl, dim3(msm_grid_(n)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(k_fb_dbl, dim3(msm_grid(n)), dim3(256), 0, stream,
                        tab + (u64)(w - 1) * n, tmp, n, MSM_FB_C);
-    hipLaunchKernelGGL(k_fb_to_aff, dim3(msm_grid_(runs, 64)), dim3(64), 0, stream, tmp,
+    hipLaunchKernelGGL(k_fb_to_aff, dim3(msm_grid(runs, 64)), dim3(64), 0, stream, tmp,
                        tab + (u64)w * n, n);
   }
 }
 
-// the reduction at one window per batch element. The level-1 kernel is the
-// generic one; with a single bucket set per MSM there is parallelism to
-// spare, so segments are short (s = 4 against the generic 16 at this bucket
-// count) and a window has up to 32 chunks, which level 2 folds with 32 lanes
-// per term. Serial chain in point operations, c=16: 6 (segment) + 8 (chunk
-// tree) + 5 (chunk fold) + 14 (doublings) + 4 (terms) = 37, against 59 with
-// the generic c=16 row (s = 16, K = 8).
+// the fixed-base plan's reduction, one bucket set per MSM. With a single set
+// there is parallelism to spare, so segments are short (s = 4 against the
+// generic 16 at this bucket count) and the set has 32 chunks, which level 2
+// folds with 32 lanes per term. Serial chain in point operations, c=16: 6
+// (segment) + 8 (chunk tree) + 5 (chunk fold) + 14 (doublings) + 4 (terms) =
+// 37, against 59 with the generic c=16 row (s = 16, K = 8).
 constexpr int MSM_FB_SEG = 4;
-constexpr int MSM_FB_WS_KMAX = 32;
-constexpr int MSM_FB_K = MSM_FB_NBUCK / MSM_FB_SEG / MSM_WS_WIDTH;
-static_assert(MSM_FB_NBUCK / MSM_FB_SEG >= MSM_WS_WIDTH && MSM_FB_K <= MSM_FB_WS_KMAX &&
-                  MSM_FB_K <= MSM_NWIN_MAX * MSM_WS_KMAX,
-              "chunks per window: level-2 lanes and the d_partials allocation");
-static_assert(1 + 8 + 5 <= MSM_WS_TERMS, "level-2 terms: T, 8 planes, 5 chunk-index planes");
 
-// level 2, lane = KMAX*e + k of the wide form (msm_wsum_input with 32 chunks)
-TG_HD VestaJac msm_fb_wsum_input(const VestaJac* chunks, int Wd, int K, int lane) {
-  const int e = lane / MSM_FB_WS_KMAX, k = lane & (MSM_FB_WS_KMAX - 1);
-  const int lgw = msm_lg2(Wd), lgk = msm_lg2(K);
-  const VestaJac* c = chunks + k * MSM_CHUNK_OUT;
-  if (k >= K) return jac_identity<FqCfg>();
-  if (e == 0) return c[0];
-  if (e <= lgw) return c[1 + e];
-  int a = e - lgw - 1;
-  if (a < lgk && ((k >> a) & 1)) return c[1];
-  return jac_identity<FqCfg>();
+// ---- the launch plan: everything the two uses of msm_run disagree about ----
+struct MsmPlan {
+  MsmCfg cfg;
+  const VestaAff* pts;  // what the accumulation gathers from: the bases, or their table
+  uint32_t stride;      // table stride N (its SRS set's size); 0: plain bases, generic plan
+  bool safe;            // accumulation that handles identities and equal x
+  int rseg, rWd, rK;    // reduction: buckets per segment, segments per chunk, chunks per set
+  // bucket sets per MSM = Jacobian points msm_run returns per MSM
+  int sets() const { return stride ? 1 : cfg.nwin; }
+};
+
+inline MsmPlan msm_plan(const MsmCfg& cfg, const VestaAff* pts, uint32_t stride, bool safe,
+                        int rseg) {
+  const int rWd = msm_ws_width(cfg.nbuck / rseg);
+  return MsmPlan{cfg, pts, stride, safe, rseg, rWd, cfg.nbuck / rseg / rWd};
 }
 
-// level 2, one block per batch element: K chunk results -> the MSM's sum
-__global__ void __launch_bounds__(MSM_WS_TERMS* MSM_FB_WS_KMAX) k_fb_window_sum(
-    const VestaJac* partials, VestaJac* wsums, int Wd, int K, int lgs) {
-  __shared__ VestaJac X[MSM_WS_TERMS * MSM_FB_WS_KMAX];
-  const int tid = threadIdx.x, k = tid & (MSM_FB_WS_KMAX - 1), e = tid / MSM_FB_WS_KMAX;
-  X[tid] = msm_fb_wsum_input(partials + (u64)blockIdx.x * K * MSM_CHUNK_OUT, Wd, K, tid);
-  __syncthreads();
-  for (int off = K / 2; off >= 1; off >>= 1) {
-    if (k < off) X[tid] = jac_add(X[tid], X[tid + off]);
-    __syncthreads();
-  }
-  VestaJac v = jac_identity<FqCfg>();
-  if (k == 0) v = msm_wsum_scale(X[tid], Wd, K, lgs, e);
-  __syncthreads();
-  if (k == 0) X[e] = v;
-  __syncthreads();
-  for (int off = MSM_WS_TERMS / 2; off >= 1; off >>= 1) {
-    if (tid < off) X[tid] = jac_add(X[tid], X[tid + off]);
-    __syncthreads();
-  }
-  if (tid == 0) wsums[blockIdx.x] = X[0];
+// nn points per MSM over plain device bases; safe for sets that may hold
+// identities or repeated points (caller uploads)
+inline MsmPlan msm_plan_generic(long nn, const VestaAff* bases, bool safe) {
+  const MsmCfg cfg = msm_cfg(nn);
+  return msm_plan(cfg, bases, 0, safe, msm_red_seg(cfg.nbuck));
 }
 
-// msm_run over a fixed-base table (msm_fb_build of an SRS set of N = tab_n
-// points): B MSMs over the first nn <= N bases. sums receives ONE Jacobian
-// point per MSM, the MSM itself: no host combine. The table's points must be
-// pairwise x-distinct (tg_load_srs checks it), for the branch-free
-// accumulation. w must be msm_work_alloc'ed for (n, B).
+// over the first nn <= tab_n bases of an SRS set, through its table
+// (msm_fb_build of tab_n points). The table's points must be pairwise
+// x-distinct (tg_load_srs checks it), for the branch-free accumulation.
+inline MsmPlan msm_plan_fixed(const VestaAff* tab, u64 tab_n) {
+  return msm_plan(MsmCfg{MSM_FB_C, MSM_FB_NWIN, MSM_FB_NBUCK, MSM_FB_NBUCK / MSM_SEG, MSM_SEG},
+                  tab, (uint32_t)tab_n, false, MSM_FB_SEG);
+}
+
+// a reduction shape that the kernels and the workspace hold: whole chunks, a
+// power-of-two K within the level-2 lanes per term, sets * K chunks within
+// d_partials, and T + planes + chunk-index planes within MSM_WS_TERMS
+constexpr bool msm_red_fits(int sets, int nbuck, int s) {
+  const int M = nbuck / s, Wd = msm_ws_width(M), K = M / Wd;
+  return K * Wd * s == nbuck && (K & (K - 1)) == 0 && K <= MSM_WS_KWIDE &&
+         sets * K <= MSM_NWIN_MAX * MSM_WS_KMAX && 1 + msm_lg2(Wd) + msm_lg2(K) <= MSM_WS_TERMS;
+}
+constexpr bool msm_plans_fit() {
+  for (int c = 8; c <= MSM_C_MAX; c++)
+    if (msm_c_generic(c) &&
+        !msm_red_fits(msm_nwin(c), 1 << (c - 1), msm_red_seg(1 << (c - 1))))
+      return false;
+  return msm_red_fits(1, MSM_FB_NBUCK, MSM_FB_SEG);
+}
+static_assert(msm_plans_fit(), "a plan's reduction outgrows level 2 or the d_partials allocation");
+
+template <int KMAX>
+inline void msm_wsum_launch(MsmWork& w, const MsmPlan& plan, u64 B, hipStream_t stream) {
+  hipLaunchKernelGGL(k_window_sum<KMAX>, dim3(plan.sets() * B), dim3(MSM_WS_TERMS * KMAX), 0,
+                     stream, w.d_partials, w.d_wsums, plan.rWd, plan.rK, msm_lg2(plan.rseg));
+}
+
+// B same-size MSMs (nn points each, n = nn * B canonical device scalars) by
+// one plan: enqueues the whole kernel chain on stream and the copy of the
+// plan.sets() * B Jacobian sums to host out (valid after the caller
+// synchronizes the stream; msm_finish turns each MSM's sets() points into
+// the MSM). w must be msm_work_alloc'ed for (n, B).
+// ProfFn: callable int->RAII scope, as in ntt_run (msm_noprof for none).
 template <class ProfFn>
-inline void msm_run_fixed(MsmWork& w, const ScalarRepr* d_scalars, u64 n, u64 nn, u64 B,
-                          const VestaAff* tab, u64 tab_n, hipStream_t stream, VestaJac* sums,
-                          ProfFn&& prof) {
-  const MsmCfg cfg = msm_fb_cfg();
-  const u64 m = (u64)cfg.nbuck * B;
+inline void msm_run(MsmWork& w, const ScalarRepr* d_scalars, u64 n, u64 nn, u64 B,
+                    const MsmPlan& plan, hipStream_t stream, VestaJac* out, ProfFn&& prof) {
+  const MsmCfg& cfg = plan.cfg;
+  const u64 m = (u64)plan.sets() * cfg.nbuck * B;
   {
     [[maybe_unused]] auto chain = prof(MSM_P_CHAIN);
     {
       [[maybe_unused]] auto p = prof(MSM_P_DIGITS);
       hipMemsetAsync(w.d_hist, 0, m * 4, stream);
       hipLaunchKernelGGL(k_digits, dim3(msm_grid(n)), dim3(256), 0, stream, d_scalars, n,
-                         nn, cfg, w.d_dig, w.d_hist, true);
+                         nn, cfg, w.d_dig, w.d_hist, plan.stride != 0);
     }
     {
       [[maybe_unused]] auto p = prof(MSM_P_SCAN);
@@ -910,7 +877,7 @@ inline void msm_run_fixed(MsmWork& w, const ScalarRepr* d_scalars, u64 n, u64 nn
     {
       [[maybe_unused]] auto p = prof(MSM_P_SCATTER);
       hipLaunchKernelGGL(k_scatter, dim3(msm_grid(n)), dim3(256), 0, stream, w.d_dig, n,
-                         nn, cfg, w.d_off, w.d_sorted, (uint32_t)tab_n);
+                         nn, cfg, w.d_off, w.d_sorted, plan.stride);
       hipMemcpyAsync(w.d_end, w.d_off, m * 4, hipMemcpyDeviceToDevice, stream);
     }
     {
@@ -918,21 +885,26 @@ inline void msm_run_fixed(MsmWork& w, const ScalarRepr* d_scalars, u64 n, u64 nn
       hipMemsetAsync(w.d_big + m, 0, 4, stream);
       const uint32_t* ord = msm_len_sort(w, m, stream);
       [[maybe_unused]] auto pk = prof(MSM_P_ACC_KERNELS);
-      msm_acc_launch<false>(w, m, tab, ord, stream);
+      if (plan.safe)
+        msm_acc_launch<true>(w, m, plan.pts, ord, stream);
+      else
+        msm_acc_launch<false>(w, m, plan.pts, ord, stream);
     }
     {
       [[maybe_unused]] auto p = prof(MSM_P_REDUCE);
-      hipLaunchKernelGGL(k_bucket_segsum, dim3(B * MSM_FB_K), dim3(MSM_WS_WIDTH), 0, stream,
-                         w.d_buckets, w.d_partials, cfg.nbuck, MSM_FB_SEG);
+      hipLaunchKernelGGL(k_bucket_segsum, dim3(plan.sets() * B * plan.rK), dim3(MSM_WS_WIDTH),
+                         0, stream, w.d_buckets, w.d_partials, cfg.nbuck, plan.rseg);
     }
     {
       [[maybe_unused]] auto p = prof(MSM_P_WSUM);
-      hipLaunchKernelGGL(k_fb_window_sum, dim3(B), dim3(MSM_WS_TERMS * MSM_FB_WS_KMAX), 0,
-                         stream, w.d_partials, w.d_wsums, MSM_WS_WIDTH, MSM_FB_K,
-                         msm_lg2(MSM_FB_SEG));
+      if (plan.rK <= MSM_WS_KMAX)
+        msm_wsum_launch<MSM_WS_KMAX>(w, plan, B, stream);
+      else
+        msm_wsum_launch<MSM_WS_KWIDE>(w, plan, B, stream);
     }
   }
-  hipMemcpyAsync(sums, w.d_wsums, sizeof(VestaJac) * B, hipMemcpyDeviceToHost, stream);
+  hipMemcpyAsync(out, w.d_wsums, sizeof(VestaJac) * plan.sets() * B, hipMemcpyDeviceToHost,
+                 stream);
 }
 
 // host-side final combine: acc = sum_w 2^(c*w) * wsum[w]  (Horner, ~240
@@ -949,6 +921,13 @@ inline VestaJac msm_host_combine_jac(const VestaJac* wsums, const MsmCfg& cfg) {
 
 inline VestaAff msm_host_combine(const VestaJac* wsums, const MsmCfg& cfg) {
   return jac_to_aff(msm_host_combine_jac(wsums, cfg));
+}
+
+// one MSM from the plan.sets() points msm_run returned for it: the Horner
+// combine of the generic plan's window sums; the fixed-base plan's one point
+// is the MSM as it came
+inline VestaJac msm_finish(const MsmPlan& plan, const VestaJac* sums) {
+  return plan.sets() > 1 ? msm_host_combine_jac(sums, plan.cfg) : sums[0];
 }
 
 }  // namespace taiga

@@ -212,28 +212,22 @@ static int gpu_msm_commit_canon(Ctx* c, long nn, int B, const VestaAff* d_bases,
   ProfScope total(c, P_MSM_TOTAL);
   // the SRS sets go through their fixed-base tables: one point per MSM comes
   // back and there is nothing to combine
-  const VestaAff* tab = d_bases == c->d_g ? c->d_g_tab : (d_bases == c->d_gl ? c->d_gl_tab : nullptr);
-  MsmCfg cfg = msm_cfg(nn);
-  const size_t per = tab ? 1 : (size_t)cfg.nwin;
-  std::vector<VestaJac> wsums(per * B);
+  const MsmPlan plan = msm_plan_for(c, d_bases, nn);
+  const size_t per = (size_t)plan.sets();
+  std::vector<VestaJac> sums(per * B);
   // only the two accumulation kernels are bracketed here (bench.py reads
   // msm_bucket_acc with profiling on; more event records would sit inside
   // its timed region)
   auto prof = [&](int idx) {
     return ProfScope(c, idx == MSM_P_ACC_KERNELS ? (int)P_MSM_ACC : -1);
   };
-  if (tab)
-    msm_run_fixed(c->msm, c->d_scalars, (u64)ntot, (u64)nn, (u64)B, tab, 1ULL << c->k,
-                  c->stream, wsums.data(), prof);
-  else
-    msm_run(c->msm, c->d_scalars, (u64)ntot, (u64)nn, (u64)B, d_bases, false, c->stream,
-            wsums.data(), prof);
+  msm_run(c->msm, c->d_scalars, (u64)ntot, (u64)nn, (u64)B, plan, c->stream, sums.data(), prof);
   if (hipStreamSynchronize(c->stream) != hipSuccess) return TG_ERR_HIP;
 #ifdef _OPENMP
 #pragma omp parallel for schedule(static)
 #endif
   for (int b = 0; b < B; b++) {
-    VestaJac acc = tab ? wsums[b] : msm_host_combine_jac(wsums.data() + (size_t)b * cfg.nwin, cfg);
+    VestaJac acc = msm_finish(plan, sums.data() + per * b);
     if (!fd_is_zero(blinds[b])) acc = jac_add(acc, wtab->mul(blinds[b]));
     outs[b] = jac_to_aff(acc);
   }

@@ -144,7 +144,8 @@ struct Ctx {
   VestaAff* d_g = nullptr;
   VestaAff* d_gl = nullptr;
   // fixed-base tables of d_g and d_gl (msm_fb_build): MSM_FB_NWIN arrays of
-  // 2^k points each, [2^(MSM_FB_C*w)] G_j. Null when k > MSM_FB_KMAX.
+  // 2^k points each, [2^(MSM_FB_C*w)] G_j. Null when k > MSM_FB_KMAX (those
+  // sets stay on the generic plan, msm_plan_for).
   VestaAff* d_g_tab = nullptr;
   VestaAff* d_gl_tab = nullptr;
   VestaAff h_w, h_u;  // Mont form, host copies
@@ -176,6 +177,17 @@ struct Ctx {
   bool pos_ready = false;  // poseidon constants uploaded to __constant__
   ProfCounter prof_c[PROF_N];
 };
+
+// the launch plan of nn-point MSMs over a device base array of this context:
+// the fixed-base plan when it is an SRS set whose table is built, else the
+// generic one. SRS bases and gen_bases output are distinct non-identity
+// points and take the branch-free accumulation; uploaded bases may hold
+// identities and duplicates and take the safe one.
+static MsmPlan msm_plan_for(const Ctx* c, const VestaAff* bases, long nn) {
+  const VestaAff* tab = bases == c->d_g ? c->d_g_tab : (bases == c->d_gl ? c->d_gl_tab : nullptr);
+  if (tab) return msm_plan_fixed(tab, 1ULL << c->k);
+  return msm_plan_generic(nn, bases, bases == c->d_bases && !c->bases_distinct);
+}
 
 static thread_local std::string g_err;
 
@@ -682,48 +694,34 @@ int tg_scalars_upload(tg_ctx* ctx, const uint8_t* scalars, size_t n) {
 }
 
 // argument and base-set checks of an MSM of n points over base_set, before
-// any allocation or launch; on TG_OK *bases is the set and *safe says whether
-// it needs the accumulation that handles identities and equal x
-static int msm_guard(const Ctx* c, size_t n, int base_set, const VestaAff** bases,
-                     bool* safe, const VestaAff** tab) {
-  *tab = nullptr;
+// any allocation or launch; on TG_OK *plan is the launch plan for that set
+static int msm_guard(const Ctx* c, size_t n, int base_set, MsmPlan* plan) {
   if (base_set < 0 || base_set > 2 || !n) return TG_ERR_BADARG;
   if (base_set == 0) {
     if (!c->d_bases || c->n_bases < n) return TG_ERR_STATE;
-    *bases = c->d_bases;
-    // custom uploaded bases may contain identities/duplicates -> SAFE variant
-    *safe = !c->bases_distinct;
   } else {
     if (c->k < 0) return TG_ERR_NOSRS;
     if (n > (1ULL << c->k)) return TG_ERR_BADARG;
-    *bases = base_set == 1 ? c->d_g : c->d_gl;
-    *tab = base_set == 1 ? c->d_g_tab : c->d_gl_tab;  // fixed-base chain if built
-    // SRS bases are distinct non-identity points -> fast branchless variant
-    *safe = false;
   }
+  const VestaAff* sets[3] = {c->d_bases, c->d_g, c->d_gl};
+  *plan = msm_plan_for(c, sets[base_set], (long)n);
   return TG_OK;
 }
 
-// the MSM of the first n resident scalars (the caller has checked them) over
-// bases, by the fixed-base chain when tab is the set's table
-static int msm_common(Ctx* c, size_t n, const VestaAff* bases, bool safe,
-                      const VestaAff* tab, uint8_t out_xy[64]) {
+// the MSM of the first n resident scalars (the caller has checked them) by plan
+static int msm_common(Ctx* c, size_t n, const MsmPlan& plan, uint8_t out_xy[64]) {
   hipError_t e;
   if ((e = msm_work_alloc(c->msm, n)) != hipSuccess) return set_err(c, "msm ws", e);
-  MsmCfg cfg = msm_cfg((long)n);
-  VestaJac wsums[32]; /* nwin <= 32 (c >= 8) */
+  VestaJac sums[32]; /* sets() <= nwin <= 32 (c >= 8) */
   // all six stages + total; the accumulation scope covers the length sort
   static const int MSM_PROF_MAP[8] = {P_MSM_DIGITS, P_MSM_SCAN,   P_MSM_SCATTER,
                                       P_MSM_ACC,    P_MSM_REDUCE, P_MSM_WSUM,
                                       -1,           P_MSM_TOTAL};
   auto prof = [&](int idx) { return ProfScope(c, MSM_PROF_MAP[idx]); };
-  if (tab)
-    msm_run_fixed(c->msm, c->d_scalars, n, n, 1, tab, 1ULL << c->k, c->stream, wsums, prof);
-  else
-    msm_run(c->msm, c->d_scalars, n, n, 1, bases, safe, c->stream, wsums, prof);
+  msm_run(c->msm, c->d_scalars, n, n, 1, plan, c->stream, sums, prof);
   hipError_t es = hipStreamSynchronize(c->stream);
   if (es != hipSuccess) return set_err(c, "msm run", es);
-  VestaAff r = tab ? jac_to_aff(wsums[0]) : msm_host_combine(wsums, cfg);
+  VestaAff r = jac_to_aff(msm_finish(plan, sums));
   if (aff_is_identity(r)) {
     memset(out_xy, 0, 64);
   } else {
@@ -737,24 +735,22 @@ static int msm_common(Ctx* c, size_t n, const VestaAff* bases, bool safe,
 int tg_msm_resident(tg_ctx* ctx, size_t n, int base_set, uint8_t out_xy[64]) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
-  const VestaAff *bases = nullptr, *tab = nullptr;
-  bool safe = true;
-  int rc = msm_guard(c, n, base_set, &bases, &safe, &tab);
+  MsmPlan plan;
+  int rc = msm_guard(c, n, base_set, &plan);
   if (rc != TG_OK) return rc;
   if (!c->d_scalars || c->n_scalars < n) return TG_ERR_STATE;
-  return msm_common(c, n, bases, safe, tab, out_xy);
+  return msm_common(c, n, plan, out_xy);
 }
 
 int tg_msm_pallas(tg_ctx* ctx, const uint8_t* scalars, size_t n, int base_set,
                   uint8_t out_xy[64]) {
   Ctx* c = (Ctx*)ctx;
   if (!c || tg_enter(c)) return TG_ERR_BADARG;
-  const VestaAff *bases = nullptr, *tab = nullptr;
-  bool safe = true;
-  int rc = msm_guard(c, n, base_set, &bases, &safe, &tab);
+  MsmPlan plan;
+  int rc = msm_guard(c, n, base_set, &plan);
   if (rc != TG_OK) return rc;
   if ((rc = tg_scalars_upload(ctx, scalars, n)) != TG_OK) return rc;
-  return msm_common(c, n, bases, safe, tab, out_xy);
+  return msm_common(c, n, plan, out_xy);
 }
 
 // ---------- NTT ----------

@@ -6,38 +6,16 @@
 //   line "# c nwin", then per 64-digit hex scalar its nwin signed digits,
 //   lowest window first, and the carry left after the top window.
 // msm_fb_probe reduce            the one-bucket-set reduction (k_bucket_segsum
-//   at MSM_FB_SEG, then k_fb_window_sum with up to 32 chunks), loops in place
-//   of lanes and blocks, against sum_d (d+1)*B_d computed another way. One
-//   line "<name> OK|FAIL" per case and batch element.
+//   at MSM_FB_SEG, then k_window_sum<32> with up to 32 chunks), loops in place
+//   of lanes and blocks (msm_probe_common.hpp), against sum_d (d+1)*B_d
+//   computed another way. One line "<name> OK|FAIL" per case and batch element.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "pasta_device.hpp"
-#include "msm.hip"
-
-using namespace taiga;
-
-static u64 sm64(u64 x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-static VestaJac mul_small(const VestaJac& p, u64 k) {
-  VestaJac acc = jac_identity<FqCfg>(), base = p;
-  while (k) {
-    if (k & 1) acc = jac_add(acc, base);
-    base = jac_dbl(base);
-    k >>= 1;
-  }
-  return acc;
-}
-
-static VestaJac pts[16];
+#include "msm_probe_common.hpp"
 
 static VestaJac naive(const VestaJac* B, int N) {
   // sum_d (d+1)*B_d by the suffix-sum walk
@@ -49,44 +27,13 @@ static VestaJac naive(const VestaJac* B, int N) {
   return acc;
 }
 
-static std::vector<VestaJac> reduce(const std::vector<VestaJac>& buckets, int B) {
-  const int N = MSM_FB_NBUCK, s = MSM_FB_SEG, Wd = MSM_WS_WIDTH, K = MSM_FB_K;
-  const int lgs = msm_lg2(s), lanes = MSM_WS_TERMS * MSM_FB_WS_KMAX;
-  // what a kernel does not write starts out as a non-identity point
-  std::vector<VestaJac> partials((size_t)B * K * MSM_CHUNK_OUT, pts[9]), sums(B);
-  for (u64 q = 0; q < (u64)B * K; q++) {  // k_bucket_segsum, block q
-    std::vector<VestaJac> lds(2 * MSM_WS_WIDTH, pts[9]);
-    VestaJac* C = lds.data();
-    VestaJac* T = C + MSM_WS_WIDTH;
-    for (int tid = 0; tid < MSM_WS_WIDTH; tid++) msm_chunk_load(buckets.data(), N, s, q, tid, C, T);
-    for (int off = Wd / 2; off >= 1; off >>= 1)
-      for (int tid = 0; tid < MSM_WS_WIDTH; tid++) msm_chunk_step(C, T, Wd, off, tid);
-    for (int tid = 0; tid < MSM_WS_WIDTH; tid++) msm_chunk_store(C, T, Wd, q, tid, partials.data());
-  }
-  for (int b = 0; b < B; b++) {  // k_fb_window_sum, block b
-    std::vector<VestaJac> X(lanes, pts[9]), v(MSM_WS_TERMS);
-    for (int tid = 0; tid < lanes; tid++)
-      X[tid] = msm_fb_wsum_input(partials.data() + (size_t)b * K * MSM_CHUNK_OUT, Wd, K, tid);
-    for (int off = K / 2; off >= 1; off >>= 1)
-      for (int tid = 0; tid < lanes; tid++)
-        if ((tid & (MSM_FB_WS_KMAX - 1)) < off) X[tid] = jac_add(X[tid], X[tid + off]);
-    for (int e = 0; e < MSM_WS_TERMS; e++)
-      v[e] = msm_wsum_scale(X[e * MSM_FB_WS_KMAX], Wd, K, lgs, e);
-    for (int e = 0; e < MSM_WS_TERMS; e++) X[e] = v[e];
-    for (int off = MSM_WS_TERMS / 2; off >= 1; off >>= 1)
-      for (int tid = 0; tid < off; tid++) X[tid] = jac_add(X[tid], X[tid + off]);
-    sums[b] = X[0];
-  }
-  return sums;
-}
-
 static int failures = 0;
 
 // single >= 0: only that bucket is occupied, and the expected sum is one
 // small multiplication
 static void check(const std::string& name, const std::vector<VestaJac>& buckets, int B,
                   int single = -1) {
-  std::vector<VestaJac> got = reduce(buckets, B);
+  std::vector<VestaJac> got = reduce<MSM_WS_KWIDE>(buckets, B, MSM_FB_NBUCK, MSM_FB_SEG);
   for (int b = 0; b < B; b++) {
     VestaAff x = jac_to_aff(got[b]);
     VestaAff y = jac_to_aff(single >= 0
@@ -99,11 +46,7 @@ static void check(const std::string& name, const std::vector<VestaJac>& buckets,
 }
 
 static int run_reduce() {
-  Fq one = fd_one_mont<FqCfg>();
-  VestaAff G;
-  G.x = fd_neg(one);  // generator (-1, 2)
-  G.y = fd_add(one, one);
-  for (int i = 0; i < 16; i++) pts[i] = mul_small(jac_from_aff(G), sm64(0xC0FFEEull + i));
+  make_table();
   const int N = MSM_FB_NBUCK;
   const VestaJac id = jac_identity<FqCfg>();
   {  // dense, two batch elements
@@ -135,7 +78,7 @@ static int run_reduce() {
 
 int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "reduce")) return run_reduce();
-  const MsmCfg cfg = msm_fb_cfg();
+  const MsmCfg cfg = msm_plan_fixed(nullptr, 1).cfg;
   printf("# %d %d\n", cfg.c, cfg.nwin);
   for (int a = 1; a < argc; a++) {
     if (strlen(argv[a]) != 64) return 2;

@@ -33,43 +33,13 @@
 #include <string>
 #include <vector>
 
-#include "pasta_device.hpp"
-#include "msm.hip"
-
-using namespace taiga;
-
-static u64 sm64(u64 x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
+#include "msm_probe_common.hpp"
 
 static std::string hex(const Fq& a) {
   char buf[65];
   snprintf(buf, sizeof buf, "%016" PRIx64 "%016" PRIx64 "%016" PRIx64 "%016" PRIx64, a.l[3],
            a.l[2], a.l[1], a.l[0]);
   return buf;
-}
-
-static VestaJac mul_small(const VestaJac& p, u64 k) {
-  VestaJac acc = jac_identity<FqCfg>(), base = p;
-  while (k) {
-    if (k & 1) acc = jac_add(acc, base);
-    base = jac_dbl(base);
-    k >>= 1;
-  }
-  return acc;
-}
-
-static VestaJac pts[16];
-
-static void make_table() {
-  Fq one = fd_one_mont<FqCfg>();
-  VestaAff G;
-  G.x = fd_neg(one);  // generator (-1, 2)
-  G.y = fd_add(one, one);
-  for (int i = 0; i < 16; i++) pts[i] = mul_small(jac_from_aff(G), sm64(0xC0FFEEull + i));
 }
 
 static std::vector<VestaJac> walk(u64 seed, int n) {
@@ -90,43 +60,11 @@ static VestaJac naive(const VestaJac* B, int N) {
   return acc;
 }
 
-// k_bucket_segsum and k_window_sum with loops in place of lanes and blocks
-static std::vector<VestaJac> reduce(const std::vector<VestaJac>& buckets, int nwin, int N) {
-  const int s = msm_red_seg(N), M = N / s, Wd = msm_ws_width(M), K = M / Wd;
-  const int lgs = msm_lg2(s), lanes = MSM_WS_TERMS * MSM_WS_KMAX;
-  // memory a kernel does not write starts out as garbage (a non-identity
-  // point): a slot read before it is written shows up in the result
-  std::vector<VestaJac> partials((size_t)nwin * K * MSM_CHUNK_OUT, pts[9]), wsums(nwin);
-  for (u64 q = 0; q < (u64)nwin * K; q++) {  // k_bucket_segsum, block q
-    std::vector<VestaJac> lds(2 * MSM_WS_WIDTH, pts[9]);
-    VestaJac* C = lds.data();
-    VestaJac* T = C + MSM_WS_WIDTH;
-    for (int tid = 0; tid < MSM_WS_WIDTH; tid++) msm_chunk_load(buckets.data(), N, s, q, tid, C, T);
-    for (int off = Wd / 2; off >= 1; off >>= 1)
-      for (int tid = 0; tid < MSM_WS_WIDTH; tid++) msm_chunk_step(C, T, Wd, off, tid);
-    for (int tid = 0; tid < MSM_WS_WIDTH; tid++) msm_chunk_store(C, T, Wd, q, tid, partials.data());
-  }
-  for (int w = 0; w < nwin; w++) {  // k_window_sum, block w
-    std::vector<VestaJac> X(lanes, pts[9]), v(MSM_WS_TERMS);
-    for (int tid = 0; tid < lanes; tid++)
-      X[tid] = msm_wsum_input(partials.data() + (size_t)w * K * MSM_CHUNK_OUT, Wd, K, tid);
-    for (int off = K / 2; off >= 1; off >>= 1)
-      for (int tid = 0; tid < lanes; tid++)
-        if ((tid & (MSM_WS_KMAX - 1)) < off) X[tid] = jac_add(X[tid], X[tid + off]);
-    for (int e = 0; e < MSM_WS_TERMS; e++) v[e] = msm_wsum_scale(X[e * MSM_WS_KMAX], Wd, K, lgs, e);
-    for (int e = 0; e < MSM_WS_TERMS; e++) X[e] = v[e];
-    for (int off = MSM_WS_TERMS / 2; off >= 1; off >>= 1)
-      for (int tid = 0; tid < off; tid++) X[tid] = jac_add(X[tid], X[tid + off]);
-    wsums[w] = X[0];
-  }
-  return wsums;
-}
-
 static int failures = 0;
 
 static void check(int c, const std::string& name, const std::vector<VestaJac>& buckets, int nwin,
                   int N) {
-  std::vector<VestaJac> got = reduce(buckets, nwin, N);
+  std::vector<VestaJac> got = reduce<MSM_WS_KMAX>(buckets, nwin, N, msm_red_seg(N));
   for (int w = 0; w < nwin; w++) {
     VestaAff a = jac_to_aff(got[w]);
     VestaAff b = jac_to_aff(naive(buckets.data() + (size_t)w * N, N));

@@ -1,10 +1,10 @@
-"""GPU tests of the fixed-base MSM chain (msm_run_fixed): MSMs over the SRS
+"""GPU tests of the fixed-base plan of msm_run (msm_plan_fixed): MSMs over the SRS
 sets g (base_set 1) and g_lagrange (base_set 2) of tests/golden/params_15 run
 over the window-shifted tables [2^(C*w)] G_j that tg_load_srs builds, with all
 windows' digits in ONE bucket set. Every case is bit-exact against the CPU
 oracle's MSM or scalar multiplication.
 
-C and NWIN restate MSM_FB_C / msm_fb_nwin of msm.hip (the host test
+C and NWIN restate MSM_FB_C / msm_nwin of msm.hip (the host test
 tests/test_msm_recode_host.py reads them from the code and pins them)."""
 import ctypes
 import random

@@ -1,5 +1,5 @@
-"""CPU-side test of the signed-digit recoding the fixed-base MSM chain relies
-on (msm.hip: msm_digit at MSM_FB_C with msm_fb_nwin windows).
+"""CPU-side test of the signed-digit recoding the fixed-base MSM plan relies
+on (msm.hip: msm_digit at MSM_FB_C with msm_nwin windows).
 
 tests/host/msm_fb_probe.cpp runs the function k_digits calls, on the host,
 for the edge scalars of msm_fb_cases.py and a few random ones. With one bucket
@@ -79,7 +79,7 @@ def test_recoding_is_exact(probe):
 
 def test_fixed_base_reduction_matches_naive(probe_bin):
     """the one-bucket-set reduction (segments of MSM_FB_SEG, up to 32 chunks
-    folded by k_fb_window_sum) against the suffix-sum walk on dense, empty and
+    folded by k_window_sum<32>) against the suffix-sum walk on dense, empty and
     all-equal bucket sets, and against one multiplication on single buckets"""
     r = subprocess.run([probe_bin, "reduce"], capture_output=True, text=True, timeout=600)
     rows = dict(ln.split() for ln in r.stdout.split("\n") if ln)
