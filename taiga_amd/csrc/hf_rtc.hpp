@@ -59,10 +59,17 @@ inline std::string hf_rtc_prelude() {
              (unsigned long long)v[3]);
     o << buf;
   }
-  char buf[128];
-  snprintf(buf, sizeof(buf), "#define FPINV 0x%llxULL\n",
-           (unsigned long long)FpCfg::INV);
-  o << buf;
+  // limbs 1..4 of the modulus in radix 2^30, for the radix-2^30 multiply
+  // (fd_mul_r30 of pasta_device.hpp, restated below; R30Cfg asserts the
+  // shape of the other limbs and of -p^-1)
+  {
+    char cb[256];
+    using K = R30Cfg<FpCfg>;
+    snprintf(cb, sizeof(cb),
+             "#define R30_P1 %uu\n#define R30_P2 %uu\n#define R30_P3 %uu\n#define R30_P4 %uu\n",
+             (unsigned)K::P1, (unsigned)K::P2, (unsigned)K::P3, (unsigned)K::P4);
+    o << cb;
+  }
   o << R"RTC(
 __device__ __forceinline__ void reduce_once(Fp& r) {
   u64 t[4]; u64 borrow = 0;
@@ -110,26 +117,57 @@ __device__ __forceinline__ Fp f_neg(Fp a) {
   }
   return r;
 }
+// Montgomery multiply in radix 2^30 with lazy 64-bit columns: see
+// fd_mul_r30 in pasta_device.hpp for the derivation
+typedef unsigned int u32;
+#define R30_MASK 0x3fffffffu
+__device__ __forceinline__ void r30_split(const Fp& a, u32 x[9]) {
+  x[0] = (u32)(a.l[0] << 7) & R30_MASK;
+  x[1] = (u32)(a.l[0] >> 23) & R30_MASK;
+  x[2] = (u32)((a.l[0] >> 53) | (a.l[1] << 11)) & R30_MASK;
+  x[3] = (u32)(a.l[1] >> 19) & R30_MASK;
+  x[4] = (u32)((a.l[1] >> 49) | (a.l[2] << 15)) & R30_MASK;
+  x[5] = (u32)(a.l[2] >> 15) & R30_MASK;
+  x[6] = (u32)((a.l[2] >> 45) | (a.l[3] << 19)) & R30_MASK;
+  x[7] = (u32)(a.l[3] >> 11) & R30_MASK;
+  x[8] = (u32)(a.l[3] >> 41);
+}
 __device__ __forceinline__ Fp f_mul(Fp a, Fp b) {
-  u64 t0=0,t1=0,t2=0,t3=0,t4=0,t5=0;
+  u32 x[9], y[9];
+  r30_split(a, x);
+  r30_split(b, y);
+  u64 col[17];
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
-    u64 bi = b.l[i]; u64 carry = 0; u128 s;
-    s = (u128)a.l[0]*bi + t0 + carry; t0=(u64)s; carry=(u64)(s>>64);
-    s = (u128)a.l[1]*bi + t1 + carry; t1=(u64)s; carry=(u64)(s>>64);
-    s = (u128)a.l[2]*bi + t2 + carry; t2=(u64)s; carry=(u64)(s>>64);
-    s = (u128)a.l[3]*bi + t3 + carry; t3=(u64)s; carry=(u64)(s>>64);
-    s = (u128)t4 + carry; t4=(u64)s; t5=(u64)(s>>64);
-    u64 m = t0 * FPINV;
-    u128 c = (u128)m*modv(0) + t0; carry=(u64)(c>>64);
-    c = (u128)m*modv(1) + t1 + carry; t0=(u64)c; carry=(u64)(c>>64);
-    c = (u128)m*modv(2) + t2 + carry; t1=(u64)c; carry=(u64)(c>>64);
-    c = (u128)m*modv(3) + t3 + carry; t2=(u64)c; carry=(u64)(c>>64);
-    c = (u128)t4 + carry; t3=(u64)c;
-    t4 = t5 + (u64)(c>>64); t5 = 0;
+  for (int k = 0; k < 17; k++) col[k] = 0;
+#pragma unroll
+  for (int i = 0; i < 9; i++)
+#pragma unroll
+    for (int j = 0; j < 9; j++) col[i + j] += (u64)x[i] * y[j];
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    u32 m = (0u - (u32)col[i]) & R30_MASK;
+    col[i] += m;
+    col[i + 1] += (u64)m * R30_P1;
+    col[i + 2] += (u64)m * R30_P2;
+    col[i + 3] += (u64)m * R30_P3;
+    col[i + 4] += (u64)m * R30_P4;
+    col[i + 8] += (u64)m << 14;
+    col[i + 1] += col[i] >> 30;
   }
-  Fp r; r.l[0]=t0; r.l[1]=t1; r.l[2]=t2; r.l[3]=t3;
-  reduce_once(r); return r;
+  u64 r[9]; u64 carry = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    u64 v = col[9 + k] + carry;
+    r[k] = v & R30_MASK;
+    carry = v >> 30;
+  }
+  r[8] = carry;
+  Fp out;
+  out.l[0] = r[0] | (r[1] << 30) | (r[2] << 60);
+  out.l[1] = (r[2] >> 4) | (r[3] << 26) | (r[4] << 56);
+  out.l[2] = (r[4] >> 8) | (r[5] << 22) | (r[6] << 52);
+  out.l[3] = (r[6] >> 12) | (r[7] << 18) | (r[8] << 48);
+  reduce_once(out); return out;
 }
 )RTC";
   return o.str();
