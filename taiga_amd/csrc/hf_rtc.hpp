@@ -41,136 +41,25 @@ struct HfRtcKernel {
   bool ready = false;
 };
 
+// The generated program starts with the text of pasta_field.hpp itself: the
+// gate kernel compiles the field arithmetic that every other kernel compiles,
+// not a restatement of it. Around it, only what pasta_device.hpp gives that
+// header: the two integer names (the runtime compiler's built-in header keeps
+// them to itself) and TG_HD.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wc23-extensions"
+static const char HF_FIELD_TEXT[] = {
+#embed "pasta_field.hpp"
+    , 0};
+#pragma clang diagnostic pop
+
 inline std::string hf_rtc_prelude() {
-  std::ostringstream o;
-  o << "typedef unsigned long long u64;\n"
-       "typedef unsigned __int128 u128;\n"
-       "struct Fp { u64 l[4]; };\n";
-  // the modulus as compile-time constants, as pasta_device.hpp has it: after
-  // unrolling, modv(i) folds, and the products with its zero limb and its
-  // 2^62 limb go away (a __constant__ array is opaque to the runtime compiler)
-  {
-    char buf[256];
-    const u64* v = FpCfg::MOD;
-    snprintf(buf, sizeof(buf),
-             "__device__ __forceinline__ constexpr u64 modv(int i) {\n"
-             "  return i == 0 ? %lluULL : i == 1 ? %lluULL : i == 2 ? %lluULL : %lluULL;\n}\n",
-             (unsigned long long)v[0], (unsigned long long)v[1], (unsigned long long)v[2],
-             (unsigned long long)v[3]);
-    o << buf;
-  }
-  // limbs 1..4 of the modulus in radix 2^30, for the radix-2^30 multiply
-  // (fd_mul_r30 of pasta_device.hpp, restated below; R30Cfg asserts the
-  // shape of the other limbs and of -p^-1)
-  {
-    char cb[256];
-    using K = R30Cfg<FpCfg>;
-    snprintf(cb, sizeof(cb),
-             "#define R30_P1 %uu\n#define R30_P2 %uu\n#define R30_P3 %uu\n#define R30_P4 %uu\n",
-             (unsigned)K::P1, (unsigned)K::P2, (unsigned)K::P3, (unsigned)K::P4);
-    o << cb;
-  }
-  o << R"RTC(
-__device__ __forceinline__ void reduce_once(Fp& r) {
-  u64 t[4]; u64 borrow = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    u128 d = (u128)r.l[i] - modv(i) - borrow;
-    t[i] = (u64)d; borrow = (u64)(d >> 64) ? 1 : 0;
-  }
-  if (!borrow) { r.l[0]=t[0]; r.l[1]=t[1]; r.l[2]=t[2]; r.l[3]=t[3]; }
-}
-__device__ __forceinline__ Fp f_add(Fp a, Fp b) {
-  u64 carry = 0; Fp r;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    u128 s = (u128)a.l[i] + b.l[i] + carry;
-    r.l[i] = (u64)s; carry = (u64)(s >> 64);
-  }
-  reduce_once(r); return r;
-}
-__device__ __forceinline__ Fp f_sub(Fp a, Fp b) {
-  u64 borrow = 0; Fp r;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    u128 d = (u128)a.l[i] - b.l[i] - borrow;
-    r.l[i] = (u64)d; borrow = (u64)(d >> 64) ? 1 : 0;
-  }
-  if (borrow) {
-    u64 c = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      u128 s = (u128)r.l[i] + modv(i) + c;
-      r.l[i] = (u64)s; c = (u64)(s >> 64);
-    }
-  }
-  return r;
-}
-__device__ __forceinline__ Fp f_neg(Fp a) {
-  bool z = !(a.l[0] | a.l[1] | a.l[2] | a.l[3]);
-  if (z) return a;
-  u64 borrow = 0; Fp r;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    u128 d = (u128)modv(i) - a.l[i] - borrow;
-    r.l[i] = (u64)d; borrow = (u64)(d >> 64) ? 1 : 0;
-  }
-  return r;
-}
-// Montgomery multiply in radix 2^30 with lazy 64-bit columns: see
-// fd_mul_r30 in pasta_device.hpp for the derivation
-typedef unsigned int u32;
-#define R30_MASK 0x3fffffffu
-__device__ __forceinline__ void r30_split(const Fp& a, u32 x[9]) {
-  x[0] = (u32)(a.l[0] << 7) & R30_MASK;
-  x[1] = (u32)(a.l[0] >> 23) & R30_MASK;
-  x[2] = (u32)((a.l[0] >> 53) | (a.l[1] << 11)) & R30_MASK;
-  x[3] = (u32)(a.l[1] >> 19) & R30_MASK;
-  x[4] = (u32)((a.l[1] >> 49) | (a.l[2] << 15)) & R30_MASK;
-  x[5] = (u32)(a.l[2] >> 15) & R30_MASK;
-  x[6] = (u32)((a.l[2] >> 45) | (a.l[3] << 19)) & R30_MASK;
-  x[7] = (u32)(a.l[3] >> 11) & R30_MASK;
-  x[8] = (u32)(a.l[3] >> 41);
-}
-__device__ __forceinline__ Fp f_mul(Fp a, Fp b) {
-  u32 x[9], y[9];
-  r30_split(a, x);
-  r30_split(b, y);
-  u64 col[17];
-#pragma unroll
-  for (int k = 0; k < 17; k++) col[k] = 0;
-#pragma unroll
-  for (int i = 0; i < 9; i++)
-#pragma unroll
-    for (int j = 0; j < 9; j++) col[i + j] += (u64)x[i] * y[j];
-#pragma unroll
-  for (int i = 0; i < 9; i++) {
-    u32 m = (0u - (u32)col[i]) & R30_MASK;
-    col[i] += m;
-    col[i + 1] += (u64)m * R30_P1;
-    col[i + 2] += (u64)m * R30_P2;
-    col[i + 3] += (u64)m * R30_P3;
-    col[i + 4] += (u64)m * R30_P4;
-    col[i + 8] += (u64)m << 14;
-    col[i + 1] += col[i] >> 30;
-  }
-  u64 r[9]; u64 carry = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    u64 v = col[9 + k] + carry;
-    r[k] = v & R30_MASK;
-    carry = v >> 30;
-  }
-  r[8] = carry;
-  Fp out;
-  out.l[0] = r[0] | (r[1] << 30) | (r[2] << 60);
-  out.l[1] = (r[2] >> 4) | (r[3] << 26) | (r[4] << 56);
-  out.l[2] = (r[4] >> 8) | (r[5] << 22) | (r[6] << 52);
-  out.l[3] = (r[6] >> 12) | (r[7] << 18) | (r[8] << 48);
-  reduce_once(out); return out;
-}
-)RTC";
-  return o.str();
+  return std::string("typedef unsigned int uint32_t;\n"
+                     "typedef unsigned long uint64_t;\n"
+                     "#define TG_HD __host__ __device__ __forceinline__\n") +
+         HF_FIELD_TEXT +
+         "using namespace taiga;\n"
+         "using Fp = Fd<FpCfg>;\n";
 }
 
 // generate the hf_gates kernel source for this desc's gate constraints.
@@ -271,21 +160,21 @@ inline std::string hf_rtc_source(const PDesc& d,
           if (stk.size() < 2) return std::string();
           std::string b = stk.back(); stk.pop_back();
           std::string a = stk.back(); stk.pop_back();
-          const char* fn = op.tag == XADD ? "f_add" : op.tag == XSUB ? "f_sub" : "f_mul";
+          const char* fn = op.tag == XADD ? "fd_add" : op.tag == XSUB ? "fd_sub" : "fd_mul";
           stk.push_back(emit(std::string(fn) + "(" + a + "," + b + ")"));
           break;
         }
         case XNEG: {
           if (stk.empty()) return std::string();
           std::string a = stk.back(); stk.pop_back();
-          stk.push_back(emit("f_neg(" + a + ")"));
+          stk.push_back(emit("fd_neg(" + a + ")"));
           break;
         }
         case XSCALE: {
           if (stk.empty() || op.a >= d.consts.size()) return std::string();
           std::string a = stk.back(); stk.pop_back();
           std::ostringstream e;
-          e << "f_mul(" << a << ",CONSTS[" << op.a << "])";
+          e << "fd_mul(" << a << ",CONSTS[" << op.a << "])";
           stk.push_back(emit(e.str()));
           break;
         }
@@ -294,7 +183,7 @@ inline std::string hf_rtc_source(const PDesc& d,
       }
     }
     if (stk.size() != 1) return std::string();
-    o << "  acc = f_add(f_mul(acc, y), " << stk.back() << ");\n";
+    o << "  acc = fd_add(fd_mul(acc, y), " << stk.back() << ");\n";
     }  // gi
     o << "  return acc;\n}\n";
   }
@@ -313,7 +202,9 @@ inline std::string hf_rtc_source(const PDesc& d,
 
 // cache key: the desc blob's hash folded with the hash of the generated
 // source text, so a change to the generator or its prelude can never load
-// a code object compiled from older text (process cache and disk cache)
+// a code object compiled from older text (process cache and disk cache).
+// The prelude is pasta_field.hpp: any edit to that header changes every key
+// and the shipped descs compile again, as intended
 inline uint64_t hf_fnv(const void* data, size_t n, uint64_t h = 1469598103934665603ULL) {
   const uint8_t* b = (const uint8_t*)data;
   for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ULL;

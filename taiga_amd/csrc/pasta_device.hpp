@@ -29,408 +29,9 @@
 // implementation to drift.
 #define TG_HD __host__ __device__ __forceinline__
 
+#include "pasta_field.hpp"  // the fields; the curves follow here
+
 namespace taiga {
-
-using u64 = uint64_t;
-using u128 = unsigned __int128;
-
-// ---- field configurations (constants generated by tools/gen_fd_const.py
-//      from the published Pasta moduli; convention pinned by tests/) ----
-struct FpCfg {  // Fp = pallas::Base = vesta::Scalar (NTT field)
-  static constexpr u64 MOD[4] = {0x992d30ed00000001ULL, 0x224698fc094cf91bULL,
-                                 0x0000000000000000ULL, 0x4000000000000000ULL};
-  static constexpr u64 R2[4] = {0x8c78ecb30000000fULL, 0xd7d30dbd8b0de0e7ULL,
-                                0x7797a99bc3c95d18ULL, 0x096d41af7b9cb714ULL};
-  static constexpr u64 INV = 0x992d30ecffffffffULL;
-  static constexpr u64 ROOT[4] = {0xbdad6fabd87ea32fULL, 0xea322bf2b7bb7584ULL,
-                                  0x362120830561f81aULL, 0x2bce74deac30ebdaULL};
-  static constexpr u64 ROOT_INV[4] = {0xf0b87c7db2ce91f6ULL, 0x84a0a1d8859f066fULL,
-                                      0xb4ed8e647196dad1ULL, 0x2cd5282c53116b5cULL};
-  static constexpr u64 T_ODD[4] = {0x094cf91b992d30edULL, 0x00000000224698fcULL,
-                                   0x0000000000000000ULL, 0x0000000040000000ULL};
-  static constexpr u64 T1_2[4] = {0x04a67c8dcc969877ULL, 0x0000000011234c7eULL,
-                                  0x0000000000000000ULL, 0x0000000020000000ULL};
-};
-
-struct FqCfg {  // Fq = vesta::Base = pallas::Scalar (Vesta coordinates)
-  static constexpr u64 MOD[4] = {0x8c46eb2100000001ULL, 0x224698fc0994a8ddULL,
-                                 0x0000000000000000ULL, 0x4000000000000000ULL};
-  static constexpr u64 R2[4] = {0xfc9678ff0000000fULL, 0x67bb433d891a16e3ULL,
-                                0x7fae231004ccf590ULL, 0x096d41af7ccfdaa9ULL};
-  static constexpr u64 INV = 0x8c46eb20ffffffffULL;
-  static constexpr u64 ROOT[4] = {0xa70e2c1102b6d05fULL, 0x9bb97ea3c106f049ULL,
-                                  0x9e5c4dfd492ae26eULL, 0x2de6a9b8746d3f58ULL};
-  static constexpr u64 ROOT_INV[4] = {0x57eecda0a84b6836ULL, 0x4ad38b9084b8a80cULL,
-                                      0xf4c8f353124086c1ULL, 0x2235e1a7415bf936ULL};
-  static constexpr u64 T_ODD[4] = {0x0994a8dd8c46eb21ULL, 0x00000000224698fcULL,
-                                   0x0000000000000000ULL, 0x0000000040000000ULL};
-  static constexpr u64 T1_2[4] = {0x04ca546ec6237591ULL, 0x0000000011234c7eULL,
-                                  0x0000000000000000ULL, 0x0000000020000000ULL};
-};
-
-// ---- field element ----
-template <class C>
-struct Fd {
-  u64 l[4];
-};
-
-template <class C>
-TG_HD bool fd_is_zero(const Fd<C>& a) {
-  return (a.l[0] | a.l[1] | a.l[2] | a.l[3]) == 0;
-}
-
-template <class C>
-TG_HD bool fd_eq(const Fd<C>& a, const Fd<C>& b) {
-  return a.l[0] == b.l[0] && a.l[1] == b.l[1] && a.l[2] == b.l[2] && a.l[3] == b.l[3];
-}
-
-// true iff the raw 256-bit value is a canonical representative (v < MOD).
-// The one input-range check for every decoder. Limb compares against the
-// constant modulus, no carry chain: the 128-bit subtract-and-borrow form
-// cost the ingestion kernels 3-6 more VGPRs.
-template <class C>
-TG_HD bool fd_is_canonical(const Fd<C>& v) {
-  bool lt = false;  // over the limbs seen so far, low to high
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-    lt = v.l[i] < C::MOD[i] || (v.l[i] == C::MOD[i] && lt);
-  return lt;
-}
-
-template <class C>
-TG_HD Fd<C> fd_zero() {
-  return Fd<C>{{0, 0, 0, 0}};
-}
-
-// r = r - MOD if r >= MOD
-template <class C>
-TG_HD void fd_reduce_once(Fd<C>& r) {
-  u64 t[4];
-  u64 borrow = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    u128 d = (u128)r.l[i] - C::MOD[i] - borrow;
-    t[i] = (u64)d;
-    borrow = (u64)(d >> 64) ? 1u : 0u;
-  }
-  if (!borrow) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) r.l[i] = t[i];
-  }
-}
-
-template <class C>
-TG_HD Fd<C> fd_add(const Fd<C>& a, const Fd<C>& b) {
-  Fd<C> r;
-  u64 carry = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    u128 s = (u128)a.l[i] + b.l[i] + carry;
-    r.l[i] = (u64)s;
-    carry = (u64)(s >> 64);
-  }
-  fd_reduce_once(r);
-  return r;
-}
-
-template <class C>
-TG_HD Fd<C> fd_sub(const Fd<C>& a, const Fd<C>& b) {
-  Fd<C> r;
-  u64 borrow = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    u128 d = (u128)a.l[i] - b.l[i] - borrow;
-    r.l[i] = (u64)d;
-    borrow = (u64)(d >> 64) ? 1u : 0u;
-  }
-  if (borrow) {
-    u64 carry = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      u128 s = (u128)r.l[i] + C::MOD[i] + carry;
-      r.l[i] = (u64)s;
-      carry = (u64)(s >> 64);
-    }
-  }
-  return r;
-}
-
-template <class C>
-TG_HD Fd<C> fd_neg(const Fd<C>& a) {
-  if (fd_is_zero(a)) return a;
-  Fd<C> r;
-  u64 borrow = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    u128 d = (u128)C::MOD[i] - a.l[i] - borrow;
-    r.l[i] = (u64)d;
-    borrow = (u64)(d >> 64) ? 1u : 0u;
-  }
-  return r;
-}
-
-// CIOS Montgomery multiply on the integer multiplier: r = a*b*R^{-1} mod m.
-// The host path, and the device path under TG_FD_MUL_INT.
-template <class C>
-TG_HD Fd<C> fd_mul_int(const Fd<C>& a, const Fd<C>& b) {
-  u64 t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    u64 bi = b.l[i];
-    u64 carry = 0;
-    u128 s;
-    s = (u128)a.l[0] * bi + t0 + carry; t0 = (u64)s; carry = (u64)(s >> 64);
-    s = (u128)a.l[1] * bi + t1 + carry; t1 = (u64)s; carry = (u64)(s >> 64);
-    s = (u128)a.l[2] * bi + t2 + carry; t2 = (u64)s; carry = (u64)(s >> 64);
-    s = (u128)a.l[3] * bi + t3 + carry; t3 = (u64)s; carry = (u64)(s >> 64);
-    s = (u128)t4 + carry; t4 = (u64)s; t5 = (u64)(s >> 64);
-
-    u64 m = t0 * C::INV;
-    u128 c = (u128)m * C::MOD[0] + t0;
-    carry = (u64)(c >> 64);
-    c = (u128)m * C::MOD[1] + t1 + carry; t0 = (u64)c; carry = (u64)(c >> 64);
-    c = (u128)m * C::MOD[2] + t2 + carry; t1 = (u64)c; carry = (u64)(c >> 64);
-    c = (u128)m * C::MOD[3] + t3 + carry; t2 = (u64)c; carry = (u64)(c >> 64);
-    c = (u128)t4 + carry; t3 = (u64)c;
-    t4 = t5 + (u64)(c >> 64);
-    t5 = 0;
-  }
-  Fd<C> r{{t0, t1, t2, t3}};
-  fd_reduce_once(r);
-  return r;
-}
-
-// ---- radix-2^30 multiply: lazy 64-bit columns, no carry flags ----
-//
-// Nine 30-bit limbs in 32-bit registers. A limb product is below 2^60, so a
-// 64-bit column takes the nine products and five reduction terms that can
-// meet in it (14 * 2^60 + carries < 2^64) without a carry-out: every
-// accumulation is one v_mad_u64_u32, and carries move once per reduction
-// step as a plain shift. Nine steps divide by 2^270; both operands are cut
-// as limbs of 2^7 a and 2^7 b, so the result is ab / 2^256 and stays below
-// 2p as in the integer form. p = 1 mod 2^32 makes -p^-1 = -1 mod 2^30: the
-// Montgomery factor of a step is a negation. p = 2^254 + t, t < 2^126, and
-// the lowest limb of p is 1: a step is an add, four limb products and a
-// shift for 2^254.
-// hf_rtc.hpp restates r30_split, the multiply and the reduction in the text
-// of the runtime-compiled prelude (f_mul): keep the two in step.
-constexpr uint32_t R30_MASK = (1u << 30) - 1;
-
-template <class C>
-struct R30Cfg {
-  static constexpr uint32_t P1 = (uint32_t)(C::MOD[0] >> 30) & R30_MASK;
-  static constexpr uint32_t P2 = (uint32_t)((C::MOD[0] >> 60) | (C::MOD[1] << 4)) & R30_MASK;
-  static constexpr uint32_t P3 = (uint32_t)(C::MOD[1] >> 26) & R30_MASK;
-  static constexpr uint32_t P4 = (uint32_t)((C::MOD[1] >> 56) | (C::MOD[2] << 8)) & R30_MASK;
-  static_assert((C::MOD[0] & R30_MASK) == 1, "limb 0 of p");
-  static_assert((C::INV & R30_MASK) == R30_MASK, "-p^-1 mod 2^30");
-  static_assert((C::MOD[2] >> 22) == 0 && C::MOD[3] == (1ULL << 62), "limbs 5..8 of p");
-};
-
-// the nine 30-bit limbs of 2^7 a
-template <class C>
-TG_HD void r30_split(const Fd<C>& a, uint32_t x[9]) {
-  x[0] = (uint32_t)(a.l[0] << 7) & R30_MASK;
-  x[1] = (uint32_t)(a.l[0] >> 23) & R30_MASK;
-  x[2] = (uint32_t)((a.l[0] >> 53) | (a.l[1] << 11)) & R30_MASK;
-  x[3] = (uint32_t)(a.l[1] >> 19) & R30_MASK;
-  x[4] = (uint32_t)((a.l[1] >> 49) | (a.l[2] << 15)) & R30_MASK;
-  x[5] = (uint32_t)(a.l[2] >> 15) & R30_MASK;
-  x[6] = (uint32_t)((a.l[2] >> 45) | (a.l[3] << 19)) & R30_MASK;
-  x[7] = (uint32_t)(a.l[3] >> 11) & R30_MASK;
-  x[8] = (uint32_t)(a.l[3] >> 41);
-}
-
-// Montgomery-reduce seventeen lazy columns by 2^270; canonical result
-template <class C>
-TG_HD Fd<C> r30_reduce(u64 col[17]) {
-  using K = R30Cfg<C>;
-#pragma unroll
-  for (int i = 0; i < 9; i++) {
-    uint32_t m = (0u - (uint32_t)col[i]) & R30_MASK;
-    col[i] += m;
-    col[i + 1] += (u64)m * K::P1;
-    col[i + 2] += (u64)m * K::P2;
-    col[i + 3] += (u64)m * K::P3;
-    col[i + 4] += (u64)m * K::P4;
-    col[i + 8] += (u64)m << 14;  // m * 2^254
-    col[i + 1] += col[i] >> 30;  // the low 30 bits are zero now
-  }
-  u64 r[9];
-  u64 carry = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    u64 v = col[9 + k] + carry;
-    r[k] = v & R30_MASK;
-    carry = v >> 30;
-  }
-  r[8] = carry;
-  Fd<C> out{{r[0] | (r[1] << 30) | (r[2] << 60), (r[2] >> 4) | (r[3] << 26) | (r[4] << 56),
-             (r[4] >> 8) | (r[5] << 22) | (r[6] << 52),
-             (r[6] >> 12) | (r[7] << 18) | (r[8] << 48)}};
-  fd_reduce_once(out);
-  return out;
-}
-
-template <class C>
-TG_HD Fd<C> fd_mul_r30(const Fd<C>& a, const Fd<C>& b) {
-  uint32_t x[9], y[9];
-  r30_split(a, x);
-  r30_split(b, y);
-  u64 col[17];
-#pragma unroll
-  for (int k = 0; k < 17; k++) col[k] = 0;
-#pragma unroll
-  for (int i = 0; i < 9; i++)
-#pragma unroll
-    for (int j = 0; j < 9; j++) col[i + j] += (u64)x[i] * y[j];
-  return r30_reduce<C>(col);
-}
-
-// 45 limb products: the off-diagonal ones summed apart and doubled
-// (4 * 2^60 doubled, the diagonal and the reduction terms stay below 2^64)
-template <class C>
-TG_HD Fd<C> fd_sqr_r30(const Fd<C>& a) {
-  uint32_t x[9];
-  r30_split(a, x);
-  u64 col[17], off[17];
-#pragma unroll
-  for (int k = 0; k < 17; k++) col[k] = off[k] = 0;
-#pragma unroll
-  for (int i = 0; i < 9; i++) {
-    col[2 * i] += (u64)x[i] * x[i];
-#pragma unroll
-    for (int j = i + 1; j < 9; j++) off[i + j] += (u64)x[i] * x[j];
-  }
-#pragma unroll
-  for (int k = 0; k < 17; k++) col[k] += off[k] << 1;
-  return r30_reduce<C>(col);
-}
-
-// The device multiplies in radix 2^30 (1.5x the CIOS form's rate on gfx950:
-// profiles/README.md, Round 8); the host shim keeps the CIOS form, which
-// suits a CPU's 64-bit multiplier. Same value, bit for bit, for operands
-// below p (tests/test_fd_mul_variants_host.py).
-template <class C>
-TG_HD Fd<C> fd_mul(const Fd<C>& a, const Fd<C>& b) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_FD_MUL_INT)
-  return fd_mul_r30(a, b);
-#else
-  return fd_mul_int(a, b);
-#endif
-}
-
-template <class C>
-TG_HD Fd<C> fd_sqr(const Fd<C>& a) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_FD_MUL_INT)
-  return fd_sqr_r30(a);
-#else
-  return fd_mul_int(a, a);
-#endif
-}
-
-template <class C>
-TG_HD Fd<C> fd_to_mont(const Fd<C>& a) {
-  Fd<C> r2;
-#pragma unroll
-  for (int i = 0; i < 4; i++) r2.l[i] = C::R2[i];
-  return fd_mul(a, r2);
-}
-
-template <class C>
-TG_HD Fd<C> fd_from_mont(const Fd<C>& a) {
-  Fd<C> one{{1, 0, 0, 0}};
-  return fd_mul(a, one);
-}
-
-template <class C>
-TG_HD Fd<C> fd_one_mont() {
-  Fd<C> one{{1, 0, 0, 0}};
-  return fd_to_mont(one);
-}
-
-// base^e, e a 4x64 LE integer (standard form); base & result Montgomery
-template <class C>
-TG_HD Fd<C> fd_pow(const Fd<C>& base, const u64 e[4]) {
-  Fd<C> acc = fd_one_mont<C>();
-  Fd<C> b = base;
-#pragma unroll 1
-  for (int limb = 0; limb < 4; limb++) {
-    u64 bits = e[limb];
-#pragma unroll 1
-    for (int i = 0; i < 64; i++) {
-      if (bits & 1) acc = fd_mul(acc, b);
-      b = fd_sqr(b);
-      bits >>= 1;
-    }
-  }
-  return acc;
-}
-
-// small-exponent pow (e < 2^32): for twiddle generation
-template <class C>
-TG_HD Fd<C> fd_pow_u64(const Fd<C>& base, u64 e) {
-  Fd<C> acc = fd_one_mont<C>();
-  Fd<C> b = base;
-  while (e) {
-    if (e & 1) acc = fd_mul(acc, b);
-    b = fd_sqr(b);
-    e >>= 1;
-  }
-  return acc;
-}
-
-template <class C>
-TG_HD Fd<C> fd_inv(const Fd<C>& a) {
-  u64 e[4];
-  u64 borrow = 0;
-  const u64 two[4] = {2, 0, 0, 0};
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    u128 d = (u128)C::MOD[i] - two[i] - borrow;
-    e[i] = (u64)d;
-    borrow = (u64)(d >> 64) ? 1u : 0u;
-  }
-  return fd_pow(a, e);
-}
-
-// Tonelli–Shanks (S = 32). Returns true + r (Mont) when a is a square.
-template <class C>
-TG_HD bool fd_sqrt(Fd<C>& r, const Fd<C>& a) {
-  if (fd_is_zero(a)) { r = fd_zero<C>(); return true; }
-  Fd<C> root;
-#pragma unroll
-  for (int i = 0; i < 4; i++) root.l[i] = C::ROOT[i];
-  Fd<C> z = fd_to_mont(root);
-  Fd<C> u = fd_pow(a, C::T_ODD);
-  Fd<C> x = fd_pow(a, C::T1_2);
-  Fd<C> onem = fd_one_mont<C>();
-  int m = 32;
-  while (!fd_eq(u, onem)) {
-    int i = 0;
-    Fd<C> t = u;
-    while (!fd_eq(t, onem)) {
-      t = fd_sqr(t);
-      i++;
-      if (i > m) return false;
-    }
-    if (i == m) return false;
-    Fd<C> b = z;
-    for (int j = 0; j < m - i - 1; j++) b = fd_sqr(b);
-    m = i;
-    z = fd_sqr(b);
-    u = fd_mul(u, z);
-    x = fd_mul(x, b);
-  }
-  r = x;
-  return true;
-}
-
-// is the STANDARD representative odd? (pasta compression sign)
-template <class C>
-TG_HD bool fd_is_odd_std(const Fd<C>& a) {
-  return (fd_from_mont(a).l[0] & 1) != 0;
-}
 
 // ---- curve: y^2 = x^3 + 5 over the cfg field ----
 // Affine in Montgomery form; (0,0) encodes the identity (x=0 is off-curve

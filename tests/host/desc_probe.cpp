@@ -4,7 +4,7 @@
 // tests/test_desc_parse.py. Calls no HIP runtime function, so it runs on a
 // machine without a GPU.
 //
-// argv[1] names a file of records; one output line per record.
+// argv[1] names a file of records; one output line per record ('R' apart).
 //   'P' u32 len, blob
 //       parse            -> "accept <the 15 header words> src=<n>" | "reject"
 //       (src = length of the generated hf_gates source, 0 = none)
@@ -15,6 +15,7 @@
 //       cache paths      -> "key <default> <one prelude character changed>
 //                            <default again>"
 //   'C'                  -> "caps <the TG_MAX_* constants>"
+//   'R'                  -> the text of hf_rtc_prelude(), as it is (many lines)
 // Every blob is copied into a heap block of exactly len bytes, so a read
 // past the end is a sanitizer report, not luck.
 
@@ -69,6 +70,11 @@ int main(int argc, char** argv) {
              TG_MAX_EXT_RATIO, TG_MAX_FIXED, TG_MAX_ADVICE, TG_MAX_INSTANCE, TG_MAX_GATES,
              TG_MAX_PERM, TG_MAX_CHUNKS, TG_MAX_LOOKUPS, TG_MAX_LK_EXPRS, TG_MAX_QUERIES,
              TG_MAX_INSTANCE_Q, TG_MAX_STACK, TG_MAX_COL_POINTS, TG_MAX_POINT_SETS);
+      continue;
+    }
+    if (mode == 'R') {
+      std::string pre = hf_rtc_prelude();
+      fwrite(pre.data(), 1, pre.size(), stdout);
       continue;
     }
     uint32_t len;

@@ -137,9 +137,10 @@ def probe(tmp_path_factory):
         check=True)
     count = [0]
 
-    def run(records):
-        """records: bytes each; returns one output line per record. A sanitizer
-        report is a non-zero exit and fails here."""
+    def run(records, raw=False):
+        """records: bytes each; returns one output line per record, or with
+        `raw` the whole output as it is. A sanitizer report is a non-zero exit
+        and fails here."""
         count[0] += 1
         path = d / f"in{count[0]}.bin"
         path.write_bytes(b"".join(records))
@@ -149,6 +150,8 @@ def probe(tmp_path_factory):
         path.unlink()
         assert r.returncode == 0 and "Sanitizer" not in r.stderr and \
             "runtime error" not in r.stderr, (r.returncode, r.stderr[-3000:])
+        if raw:
+            return r.stdout
         lines = r.stdout.split("\n")[:-1]
         assert len(lines) == len(records)
         return lines
@@ -466,6 +469,37 @@ def test_cache_key_follows_the_generated_source(probe):
         d, f = os.path.split(p)
         assert d == "tests/golden" and f.startswith("hf_") and f.endswith(".hsaco")
         assert len(f) == len("hf_") + 16 + len(".hsaco")
+
+
+CSRC = os.path.join(REPO, "taiga_amd", "csrc")
+
+
+def test_prelude_is_the_field_header(probe):
+    """the generated program's prelude holds the bytes of pasta_field.hpp
+    exactly once, and nothing with a body besides: what is left around them
+    (two typedefs, a define, using-declarations) has no '{', so no function
+    the header defines can be stated a second time"""
+    header = open(os.path.join(CSRC, "pasta_field.hpp"), "rb").read().decode()
+    pre = probe([b"R"], raw=True)
+    assert len(header) > 5000 and pre.count(header) == 1
+    rest = pre.replace(header, "")
+    assert "{" not in rest and len(rest) < 400, rest
+
+
+def test_generated_program_compiles(blobs, tmp_path):
+    """hf_cache_tool, the plain build's, turns the smallest edge circuit into
+    a code object: a field header that the runtime compiler refuses fails
+    here, not as a quiet fall-back to the interpreter on the GPU"""
+    subprocess.run(["make", "-C", CSRC, "hf_cache_tool", f"HIPCC={HIPCC}"], check=True,
+                   capture_output=True)
+    desc = tmp_path / "depth8.desc"
+    desc.write_bytes(blobs["depth8"])
+    r = subprocess.run([os.path.join(CSRC, "hf_cache_tool"), str(desc)], capture_output=True,
+                       text=True, timeout=600, env=dict(os.environ, TG_HF_CACHE=str(tmp_path)))
+    assert r.returncode == 0 and "compile failed" not in r.stderr, (r.stdout, r.stderr[-3000:])
+    assert " -> " in r.stdout, r.stdout
+    path = r.stdout.split(" -> ")[1].split(" (")[0]
+    assert os.path.dirname(path) == str(tmp_path) and os.path.getsize(path) > 0
 
 
 def test_gen_output_is_unchanged():
