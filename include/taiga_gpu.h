@@ -311,7 +311,9 @@ int tg_ptx_verify(tg_ctx* ctx, int slot_compliance, int slot_rl,
  * names: "msm_digits", "msm_scan", "msm_scatter", "msm_bucket_acc",
  *        "msm_reduce", "msm_wsum", "ntt_stage", "ntt_fused", "ntt_bitrev",
  *        "ntt_scale", "msm_total", "ntt_total", "gp_terms", "gp_inverse",
- *        "gp_scan" (the grand-product kernels of a proof) */
+ *        "gp_scan" (the grand-product kernels of a proof), "lk_compress",
+ *        "lk_sort", "lk_permute" (the lookup argument's compress, sort and
+ *        A' / S' construction of a proof) */
 void tg_prof_enable(tg_ctx* ctx, int on);
 void tg_prof_reset(tg_ctx* ctx);
 int tg_prof_get(tg_ctx* ctx, const char* name, double* total_ms, long* count);
@@ -364,7 +366,13 @@ int tg_ipa_open_probe(tg_ctx* ctx, uint32_t k, const uint8_t* poly, const uint8_
  * tg_lookup_product_probe: the lookup grand product of the compressed
  *   expressions a, s against their permuted forms ap, sp (2^k rows each):
  *   z[0] = 1, z[i+1] = z[i] (a_i + beta)(s_i + gamma) /
- *   ((ap_i + beta)(sp_i + gamma)); z_out = u + 1 elements. */
+ *   ((ap_i + beta)(sp_i + gamma)); z_out = u + 1 elements.
+ * tg_lookup_permute_probe: permute_expression_pair over u rows: ap_out is a
+ *   sorted ascending as canonical integers; sp_out[i] = ap_out[i] wherever
+ *   ap_out takes a new value, and the elements of s left over, in sorted
+ *   order, in the other rows (sp_out is a permutation of s). No 2^k rows
+ *   here: a and s are u elements each, 1 <= u <= 2^24. TG_ERR_BADARG when
+ *   some element of a is missing from s; the outputs are then unspecified. */
 int tg_fp_batch_inverse(tg_ctx* ctx, uint8_t* vals, size_t n);
 int tg_fp_prefix_product(tg_ctx* ctx, const uint8_t* ratios, const uint64_t* seg_lens,
                          size_t nseg, const uint8_t init[32], uint8_t* z_out);
@@ -376,6 +384,8 @@ int tg_lookup_product_probe(tg_ctx* ctx, uint32_t k, uint64_t u, const uint8_t* 
                             const uint8_t* s, const uint8_t* ap, const uint8_t* sp,
                             const uint8_t beta[32], const uint8_t gamma[32],
                             uint8_t* z_out);
+int tg_lookup_permute_probe(tg_ctx* ctx, uint64_t u, const uint8_t* a, const uint8_t* s,
+                            uint8_t* ap_out, uint8_t* sp_out);
 
 /* tg_key_gate_path: how the SELECTED key folds its gate constraints into
  *   the quotient: 1 = the hf_gates kernel specialized to the circuit at

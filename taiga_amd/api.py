@@ -152,6 +152,8 @@ def load_library():
             ctypes.c_uint32] + [ctypes.c_char_p] * 5
         lib.tg_lookup_product_probe.argtypes = [
             ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64] + [ctypes.c_char_p] * 7
+        lib.tg_lookup_permute_probe.argtypes = [
+            ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_char_p] * 4
         _lib = lib
     return _lib
 
@@ -464,6 +466,19 @@ class TaigaGpu:
         self._ck(self._lib.tg_lookup_product_probe(
             self._h, k, u, a, s, ap, sp, beta, gamma, out))
         return out.raw
+
+    def lookup_permute_probe(self, a: bytes, s: bytes):
+        """permute_expression_pair of the lookup argument over
+        u = len(a) // 32 rows: (A', S') with A' the ascending sort of a and
+        S' the matching permutation of s. TG_ERR_BADARG when an element of a
+        is missing from s."""
+        u = len(a) // 32
+        if len(a) != len(s):
+            raise ValueError("a and s must hold the same number of elements")
+        ap = ctypes.create_string_buffer(max(1, 32 * u))
+        sp = ctypes.create_string_buffer(max(1, 32 * u))
+        self._ck(self._lib.tg_lookup_permute_probe(self._h, u, a, s, ap, sp))
+        return ap.raw[: 32 * u], sp.raw[: 32 * u]
 
     # --- profiling ---
     def prof_enable(self, on=True):

@@ -39,6 +39,14 @@ struct ProverDev {
   GpPermArgs gp_perm_h;
   GpLookupArgs gp_lk_h;
   std::vector<uint8_t> gp_scan_h;
+  // lookup argument (lookup_argument.hip): the 32-bit work arrays of the S'
+  // construction (error word, flags, their scan, leftover positions, block
+  // sums), the host copy of the error word, and the device argument block of
+  // k_lk_compress (built once per key)
+  uint32_t* lk_ws = nullptr;
+  size_t lk_ws_cap = 0;
+  uint32_t lk_err_h = 0;
+  void* d_lkargs = nullptr;
   NttPlan plan_n, plan_ext;
   long ext_n = 0, n = 0;
 };
@@ -111,6 +119,8 @@ static void pdev_free(ProverDev& pd) {
   if (pd.d_stage) hipFree(pd.d_stage);
   if (pd.d_small) hipFree(pd.d_small);
   if (pd.d_hargs) hipFree(pd.d_hargs);
+  if (pd.lk_ws) hipFree(pd.lk_ws);
+  if (pd.d_lkargs) hipFree(pd.d_lkargs);
   if (pd.sc_stage) hipFree(pd.sc_stage);
   if (pd.ws0) hipFree(pd.ws0);
   if (pd.ws1) hipFree(pd.ws1);
@@ -450,6 +460,85 @@ static int dev_gp_scan(Ctx* c, ProverDev& pd, const Fp* d_a, const Fp* d_b,
   return 0;
 }
 
+// ---------------- lookup-argument launchers (kernels: lookup_argument.hip) --
+// Same conventions again. Everything is enqueued on the context's stream.
+
+static_assert(LK_MAX_LOOKUPS == TG_MAX_LOOKUPS,
+              "lookup_argument.hip tables and the pdesc_parse limits disagree");
+// largest array the sort and the 32-bit ranks are sized for
+constexpr long LK_MAX_U = 1L << 24;
+static_assert(TG_MAX_K <= 24, "LK_MAX_U must cover every key's row count");
+
+// d_dst[a] <- the ascending canonical sort of d_src[a][0..u) (Montgomery
+// form) padded to np keys with the all-ones key; np is a power of two >= u
+// and d_dst[a] is np long; no source is a destination. All arrays go through
+// the same lk_sort_launches(np) launches.
+static int dev_lk_sort(Ctx* c, int narr, const Fp* const* d_src, Fp* const* d_dst, long u,
+                       long np) {
+  if (narr < 1 || narr > LK_MAX_ARRAYS || u < 1 || np < u || np > LK_MAX_U ||
+      (np & (np - 1)) != 0)
+    return TG_ERR_BADARG;
+  LkSortArgs A{};
+  for (int a = 0; a < narr; a++) {
+    A.src[a] = d_src[a];
+    A.dst[a] = d_dst[a];
+  }
+  A.u = u;
+  A.np = np;
+  const long tl = lk_tile_len(np);
+  const dim3 tiles((unsigned)lk_tiles(np), (unsigned)narr);
+  ProfScope ps(c, P_LK_SORT);
+  hipLaunchKernelGGL(k_lk_sort_tile, tiles, dim3(LK_B), 0, c->stream, A);
+  for (long k = 2 * tl; k <= np; k <<= 1) {
+    for (long j = k / 2; j >= tl; j >>= 1)
+      hipLaunchKernelGGL(k_lk_sort_global, dim3((unsigned)lk_stage_blocks(np), (unsigned)narr),
+                         dim3(LK_B), 0, c->stream, A, k, j);
+    hipLaunchKernelGGL(k_lk_sort_merge, tiles, dim3(LK_B), 0, c->stream, A, k);
+  }
+  return 0;
+}
+
+// For every lookup: d_ap[l] holds the sorted canonical A' and d_t[l] the
+// sorted canonical table (dev_lk_sort output), u rows each. Writes S' to
+// d_sp[l] and turns d_ap[l] into Montgomery form, rows < u. An input value
+// that the table lacks sets the device error word; dev_lk_fetch_err brings
+// it to pd.lk_err_h, valid after the caller's next stream synchronisation.
+static int dev_lk_permute(Ctx* c, ProverDev& pd, int nlk, Fp* const* d_ap,
+                          const Fp* const* d_t, Fp* const* d_sp, long u) {
+  if (nlk < 1 || nlk > LK_MAX_LOOKUPS || u < 1 || u > LK_MAX_U) return TG_ERR_BADARG;
+  const size_t m = (size_t)2 * nlk * u;  // flat flags: first[], taken[] per lookup
+  const size_t nb1 = (m + 511) / 512, nb2 = (nb1 + 511) / 512;
+  // error word (padded to 4 words) | flags | scan | lpos | block sums
+  const size_t need = 4 + 2 * m + (size_t)nlk * u + nb1 + nb2;
+  uint32_t* ws = pdev_grow(c, pd.lk_ws, pd.lk_ws_cap, need);
+  if (!ws) return TG_ERR_NOMEM;
+  LkPermArgs A{};
+  for (int l = 0; l < nlk; l++) {
+    A.ap[l] = d_ap[l];
+    A.t[l] = d_t[l];
+    A.sp[l] = d_sp[l];
+  }
+  A.err = ws;
+  A.flags = ws + 4;
+  A.scan = A.flags + m;
+  A.lpos = A.scan + m;
+  uint32_t* bsum = A.lpos + (size_t)nlk * u;
+  A.u = u;
+  const dim3 grid((unsigned)lk_row_blocks(u), (unsigned)nlk);
+  ProfScope ps(c, P_LK_PERMUTE);
+  // clears the error word for this proof and the taken[] flags
+  hipMemsetAsync(ws, 0, (4 + m) * sizeof(uint32_t), c->stream);
+  hipLaunchKernelGGL(k_lk_first, grid, dim3(LK_B), 0, c->stream, A);
+  msm_scan(A.flags, A.scan, bsum, (u64)m, c->stream);
+  hipLaunchKernelGGL(k_lk_leftover, grid, dim3(LK_B), 0, c->stream, A);
+  hipLaunchKernelGGL(k_lk_write, grid, dim3(LK_B), 0, c->stream, A);
+  return 0;
+}
+
+static void dev_lk_fetch_err(Ctx* c, ProverDev& pd) {
+  hipMemcpyAsync(&pd.lk_err_h, pd.lk_ws, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+}
+
 // The IPA rounds over the first 2^k bases of d_g, on device vectors d_pp
 // (the polynomial), d_bvec (powers of the opening point) and d_wfold (ones
 // on entry), all 2^k long and folded in place. L_j / R_j are MSMs over the
@@ -752,6 +841,47 @@ __global__ void __launch_bounds__(256, 1) k_h_fold(const HFoldArgs* __restrict__
   }
 }
 
+// ---------------- lookup compress (Lagrange rows) ----------------
+// The compressed input and table expressions of every lookup over the usable
+// rows, through the same flattened programs and register stack as the h-fold.
+// The argument block is an HFoldArgs whose columns are the Lagrange pool
+// slots: rotation stride rs = 1 and mask ext_n - 1 = n - 1, and only the
+// first n_queries = h_nq_lk queries (the ones lookups use) are preloaded.
+// theta changes per proof and is a kernel argument; the block is per key.
+
+struct LkCompressOut {
+  Fp* a[TG_MAX_LOOKUPS];
+  Fp* s[TG_MAX_LOOKUPS];
+};
+
+// a[l][i], s[l][i] = Horner in theta over lookup l's input / table
+// expressions at row i < u; rows >= u are never read and stay as they are
+__global__ void __launch_bounds__(256) k_lk_compress(const HFoldArgs* __restrict__ Ap, Fp theta,
+                                                     long u, LkCompressOut out) {
+  const HFoldArgs& A = *Ap;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < u;
+       i += (long)gridDim.x * blockDim.x) {
+    Fp qv[HF_MAX_Q];
+    for (int q = 0; q < A.n_queries; q++) {
+      DevQuery dq = A.queries[q];
+      long r = (i + (long)dq.rot * A.rs) & (A.ext_n - 1);
+      const Fp* col = dq.kind == 0 ? A.fixed_cols[dq.col]
+                      : dq.kind == 1 ? A.advice_cols[dq.col] : A.inst_cols[dq.col];
+      qv[q] = col[r];
+    }
+    for (int l = 0; l < A.nlk; l++) {
+      Fp acomp = fd_zero<FpCfg>();
+      for (int e = 0; e < A.lk_nin[l]; e++)
+        acomp = fd_add(fd_mul(acomp, theta), dev_expr_eval(A, A.lk_in[l][e], i, qv));
+      Fp scomp = fd_zero<FpCfg>();
+      for (int e = 0; e < A.lk_ntab[l]; e++)
+        scomp = fd_add(fd_mul(scomp, theta), dev_expr_eval(A, A.lk_tab[l][e], i, qv));
+      out.a[l][i] = acomp;
+      out.s[l][i] = scomp;
+    }
+  }
+}
+
 
 // ---------------- product proving key ----------------
 
@@ -786,15 +916,20 @@ struct PPk {
 };
 
 // Slot numbers of the Lagrange pool (pd.lag), from the descriptor alone:
-//   sigma columns | fixed columns of the permutation      (once per key)
-//   advice | instance | z (chunks, then lookups)          (per proof)
+//   sigma columns | fixed columns of the permutation and of the
+//                   lookup expressions, one slot each         (once per key)
+//   advice | instance | z (chunks, then lookups)              (per proof)
 //   per lookup A', S', A, S | flat num | flat den
-// The advice slots, the z slots and each A', S' pair are contiguous: a
-// batched commit reads them as one concatenation.
+//   per lookup the sorted table (scratch of the A' / S' construction)
+// n_perm + (fixed columns used) + n_advice + 1 + 3 * nz + 5 * n_lookups
+// slots in all. The advice slots, the z slots and each A', S' pair are
+// contiguous: a batched commit reads them as one concatenation.
 struct LagLayout {
-  int sigma = 0, fixed = 0, adv = 0, inst = 0, z = 0, lk = 0, num = 0, den = 0, total = 0;
+  int sigma = 0, fixed = 0, adv = 0, inst = 0, z = 0, lk = 0, num = 0, den = 0, lkt = 0,
+      total = 0;
   int nz = 0;
-  std::vector<int> fixed_slot;  // per fixed column, -1 if not permuted
+  // per fixed column, -1 if neither permuted nor queried by a lookup
+  std::vector<int> fixed_slot;
   explicit LagLayout(const PDesc& d) {
     int nchunks = (d.n_perm + d.chunk_len - 1) / d.chunk_len;
     nz = nchunks + d.n_lookups;
@@ -805,13 +940,22 @@ struct LagLayout {
       auto [kind, idx] = d.perm_cols[j];
       if (kind == 1 && fixed_slot[idx] < 0) fixed_slot[idx] = fixed + nfp++;
     }
+    auto lookup_fixed = [&](const PExpr& e) {
+      for (const auto& op : e.ops)
+        if (op.tag == XFIXED && fixed_slot[op.a] < 0) fixed_slot[op.a] = fixed + nfp++;
+    };
+    for (const auto& lk_ : d.lookups) {
+      for (const auto& e : lk_.in) lookup_fixed(e);
+      for (const auto& e : lk_.tab) lookup_fixed(e);
+    }
     adv = fixed + nfp;
     inst = adv + d.n_advice;
     z = inst + 1;
     lk = z + nz;
     num = lk + 4 * d.n_lookups;
     den = num + nz;
-    total = den + nz;
+    lkt = den + nz;
+    total = lkt + d.n_lookups;
   }
 };
 
@@ -1140,6 +1284,36 @@ static int ppk_keygen(Ctx* c, PPk& pk, const uint8_t* desc, size_t desc_len) {
     for (int j = 0; j < d.n_perm; j++) up(L.sigma + j, pk.sigma_lag[j]);
     for (int col = 0; col < d.n_fixed; col++)
       if (L.fixed_slot[col] >= 0) up(L.fixed_slot[col], d.fixed_lag[col]);
+    // the argument block of k_lk_compress: the lookup programs over the
+    // pool's Lagrange columns (a fixed column no lookup queries stays null)
+    if (d.n_lookups > 0) {
+      ProverDev& pd = pk.pd;
+      HFoldArgs A{};  // uploaded before the synchronisation below
+      A.ext_n = n;
+      A.rs = 1;
+      A.nlk = d.n_lookups;
+      A.n_consts = d.n_consts;
+      A.ops = pk.d_ops;
+      A.consts = pk.d_consts;
+      A.queries = pk.d_queries;
+      A.n_queries = pk.h_nq_lk;
+      for (int l = 0; l < d.n_lookups; l++) {
+        A.lk_nin[l] = (int)pk.lk_in_de[l].size();
+        A.lk_ntab[l] = (int)pk.lk_tab_de[l].size();
+        for (size_t e = 0; e < pk.lk_in_de[l].size(); e++) A.lk_in[l][e] = pk.lk_in_de[l][e];
+        for (size_t e = 0; e < pk.lk_tab_de[l].size(); e++)
+          A.lk_tab[l][e] = pk.lk_tab_de[l][e];
+      }
+      for (int col = 0; col < d.n_fixed; col++)
+        if (L.fixed_slot[col] >= 0) A.fixed_cols[col] = pd.lag + (size_t)L.fixed_slot[col] * n;
+      for (int col = 0; col < d.n_advice; col++)
+        A.advice_cols[col] = pd.lag + (size_t)(L.adv + col) * n;
+      A.inst_cols[0] = pd.lag + (size_t)L.inst * n;
+      if (!pd.d_lkargs && hipMalloc(&pd.d_lkargs, sizeof(HFoldArgs)) != hipSuccess)
+        return TG_ERR_NOMEM;
+      if (hipMemcpy(pd.d_lkargs, &A, sizeof(HFoldArgs), hipMemcpyHostToDevice) != hipSuccess)
+        return TG_ERR_HIP;
+    }
     if (hipStreamSynchronize(c->stream) != hipSuccess) return TG_ERR_HIP;
   }
   pk.ready = true;
@@ -1270,16 +1444,6 @@ static Fp ph_fold_row(const PHRow& r) {
 
 // ---------------- the product prove ----------------
 
-static int cmp_scalar_std(const void* a, const void* b) {
-  const u64* x = (const u64*)a;
-  const u64* y = (const u64*)b;
-  for (int i = 3; i >= 0; i--) {
-    if (x[i] < y[i]) return -1;
-    if (x[i] > y[i]) return 1;
-  }
-  return 0;
-}
-
 struct PMQuery {
   int poly_id;
   Fp point, eval;
@@ -1306,7 +1470,18 @@ struct StageTimer {
     hipStreamSynchronize(stream);
     double t = now();
     fprintf(stderr, "# stage %-22s %8.2f ms\n", name, (t - last) * 1e3);
-    last = t;
+    last = sub_last = t;
+  }
+  // a mark inside a stage: the time since the previous mark of either kind;
+  // the enclosing stage's own mark still reports the whole stage
+  double sub_last = 0;
+  void sub(const char* name) {
+    if (!on) return;
+    hipStreamSynchronize(stream);
+    double t = now();
+    fprintf(stderr, "# substage %-19s %8.2f ms\n", name,
+            (t - (sub_last > last ? sub_last : last)) * 1e3);
+    sub_last = t;
   }
 };
 
@@ -1388,80 +1563,66 @@ static int pprove_core(Ctx* c, PPk& pk, std::vector<Fp>& inst_lag,
   st_.mark("advice_commit+ext");
   Fp theta = ts.squeeze();
 
-  // 3. lookups
-  std::vector<std::vector<Fp>> lkA(nlk), lkS(nlk), lkAp(nlk), lkSp(nlk);
+  // 3. lookups, on the device (lookup_argument.hip): compress A and S over
+  // the usable rows, sort A into A' and S into the table scratch, build S'.
+  // Rows u..n-1 of A' and S' are blinding drawn here in the order the host
+  // loops drew them: per lookup the A' rows, the S' rows, the A' blind, the
+  // S' blind. The draws do not depend on the values, so nothing waits for
+  // the kernels; the uploads are ordered after them on the stream, where
+  // they overwrite the sort's padding.
   std::vector<Fp> lkAp_blind(nlk), lkSp_blind(nlk);
-  {
-    PEvalCtx ec{&d, d.fixed_lag.data(), advice_lag.data(), &inst_lag, n, 1};
+  if (nlk > 0) {
+    if (!pd.d_lkargs) return TG_ERR_STATE;
+    LkCompressOut co{};
+    const Fp* srt_src[LK_MAX_ARRAYS];
+    Fp *srt_dst[LK_MAX_ARRAYS], *pap[TG_MAX_LOOKUPS], *psp[TG_MAX_LOOKUPS];
+    const Fp* pt[TG_MAX_LOOKUPS];
     for (int l = 0; l < nlk; l++) {
-      lkA[l].resize(n);
-      lkS[l].resize(n);
-      lkAp[l].resize(n);
-      lkSp[l].resize(n);
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-      for (long i = 0; i < n; i++) {
-        Fp acc = fd_zero<FpCfg>();
-        for (const auto& e : d.lookups[l].in)
-          acc = fd_add(fd_mul(acc, theta), pexpr_eval(e, ec, i));
-        lkA[l][i] = acc;
-        acc = fd_zero<FpCfg>();
-        for (const auto& e : d.lookups[l].tab)
-          acc = fd_add(fd_mul(acc, theta), pexpr_eval(e, ec, i));
-        lkS[l][i] = acc;
-      }
-      // permute_expression_pair (std form sort + leftover fill)
-      std::vector<Fp> ain(u), tsort(u);
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-      for (long i = 0; i < u; i++) {
-        ain[i] = fd_from_mont(lkA[l][i]);
-        tsort[i] = fd_from_mont(lkS[l][i]);
-      }
-      qsort(ain.data(), (size_t)u, 32, cmp_scalar_std);
-      qsort(tsort.data(), (size_t)u, 32, cmp_scalar_std);
-      std::vector<Fp> sperm(u), leftover;
-      std::vector<long> repeat_slots;
-      leftover.reserve(u);
-      long j = 0;
-      for (long i = 0; i < u; i++) {
-        if (i == 0 || cmp_scalar_std(&ain[i], &ain[i - 1]) != 0) {
-          while (j < u && cmp_scalar_std(&tsort[j], &ain[i]) < 0) leftover.push_back(tsort[j++]);
-          if (j >= u || cmp_scalar_std(&tsort[j], &ain[i]) != 0) return TG_ERR_BADARG;
-          sperm[i] = tsort[j++];
-        } else {
-          repeat_slots.push_back(i);
-        }
-      }
-      while (j < u) leftover.push_back(tsort[j++]);
-      if ((long)leftover.size() != (long)repeat_slots.size()) return TG_ERR_BADARG;
-      for (size_t r = 0; r < repeat_slots.size(); r++) sperm[repeat_slots[r]] = leftover[r];
-#ifdef _OPENMP
-#pragma omp parallel for schedule(static)
-#endif
-      for (long i = 0; i < u; i++) {
-        lkAp[l][i] = fd_to_mont(ain[i]);
-        lkSp[l][i] = fd_to_mont(sperm[i]);
-      }
-      for (long i = u; i < n; i++) lkAp[l][i] = rng.field<FpCfg>();
-      for (long i = u; i < n; i++) lkSp[l][i] = rng.field<FpCfg>();
+      pap[l] = lslot(LG.lk + 4 * l);
+      psp[l] = lslot(LG.lk + 4 * l + 1);
+      co.a[l] = lslot(LG.lk + 4 * l + 2);
+      co.s[l] = lslot(LG.lk + 4 * l + 3);
+      pt[l] = lslot(LG.lkt + l);
+      srt_src[2 * l] = co.a[l];
+      srt_dst[2 * l] = pap[l];
+      srt_src[2 * l + 1] = co.s[l];
+      srt_dst[2 * l + 1] = lslot(LG.lkt + l);
+    }
+    {
+      ProfScope ps(c, P_LK_COMPRESS);
+      hipLaunchKernelGGL(k_lk_compress, dim3(ntt_grid(u)), dim3(256), 0, c->stream,
+                         (const HFoldArgs*)pd.d_lkargs, theta, u, co);
+    }
+    st_.sub("lk_compress");
+    int rc = dev_lk_sort(c, 2 * nlk, srt_src, srt_dst, u, n);
+    if (!rc) rc = dev_lk_permute(c, pd, nlk, pap, pt, psp, u);
+    if (rc) return rc;
+    const long nblind = n - u;
+    std::vector<Fp> lk_tail((size_t)2 * nlk * nblind);  // outlives the next sync
+    for (int l = 0; l < nlk; l++) {
+      Fp* ta = lk_tail.data() + (size_t)2 * l * nblind;
+      Fp* tsp = ta + nblind;
+      for (long i = 0; i < nblind; i++) ta[i] = rng.field<FpCfg>();
+      for (long i = 0; i < nblind; i++) tsp[i] = rng.field<FpCfg>();
       lkAp_blind[l] = rng.field<FpCfg>();
       lkSp_blind[l] = rng.field<FpCfg>();
-      // A', S' side by side for the commit; A, S for the grand product
-      lag_up(LG.lk + 4 * l, lkAp[l]);
-      lag_up(LG.lk + 4 * l + 1, lkSp[l]);
-      lag_up(LG.lk + 4 * l + 2, lkA[l]);
-      lag_up(LG.lk + 4 * l + 3, lkS[l]);
+      hipMemcpyAsync(pap[l] + u, ta, nblind * sizeof(Fp), hipMemcpyHostToDevice, c->stream);
+      hipMemcpyAsync(psp[l] + u, tsp, nblind * sizeof(Fp), hipMemcpyHostToDevice, c->stream);
+    }
+    // the error word travels back with the first commit's synchronisation
+    dev_lk_fetch_err(c, pd);
+    st_.sub("lk_sort_permute");
+    for (int l = 0; l < nlk; l++) {
       Fp blds[2] = {lkAp_blind[l], lkSp_blind[l]};
       VestaAff cms[2];
-      if (gpu_msm_commit_batch_dev(c, lslot(LG.lk + 4 * l), n, 2, c->d_gl, blds, cms,
-                                   &pk.wtab))
+      if (gpu_msm_commit_batch_dev(c, pap[l], n, 2, c->d_gl, blds, cms, &pk.wtab))
         return TG_ERR_HIP;
+      // an input value that the table lacks
+      if (pd.lk_err_h) return TG_ERR_BADARG;
       if (ts.write_point(cms[0])) return TG_ERR_BADARG;
       if (ts.write_point(cms[1])) return TG_ERR_BADARG;
     }
+    st_.sub("lk_commit");
   }
 
   st_.mark("lookup_permute");

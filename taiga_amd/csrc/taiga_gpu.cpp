@@ -22,6 +22,7 @@
 #include "ntt.hip"
 #include "openings.hip"
 #include "grand_products.hip"
+#include "lookup_argument.hip"
 #include "poseidon.hip"
 #include "binding_sig.hpp"
 #include "tx_wire.hpp"
@@ -129,7 +130,8 @@ struct ProfCounter {
 static const char* const PROF_NAMES[] = {
     "msm_digits", "msm_scan",  "msm_scatter", "msm_bucket_acc", "msm_reduce",
     "msm_wsum",   "ntt_stage", "ntt_fused",   "ntt_bitrev",     "ntt_scale",
-    "msm_total",  "ntt_total", "gp_terms",    "gp_inverse",     "gp_scan"};
+    "msm_total",  "ntt_total", "gp_terms",    "gp_inverse",     "gp_scan",
+    "lk_compress", "lk_sort",  "lk_permute"};
 constexpr int PROF_N = sizeof(PROF_NAMES) / sizeof(PROF_NAMES[0]);
 
 struct PPk;
@@ -237,8 +239,9 @@ enum {
   P_MSM_DIGITS = 0, P_MSM_SCAN, P_MSM_SCATTER, P_MSM_ACC, P_MSM_REDUCE,
   P_MSM_WSUM, P_NTT_STAGE, P_NTT_FUSED, P_NTT_BITREV, P_NTT_SCALE,
   P_MSM_TOTAL, P_NTT_TOTAL, P_GP_TERMS, P_GP_INVERSE, P_GP_SCAN,
+  P_LK_COMPRESS, P_LK_SORT, P_LK_PERMUTE,
 };
-static_assert(P_GP_SCAN + 1 == PROF_N, "PROF_NAMES and the P_* indices disagree");
+static_assert(P_LK_PERMUTE + 1 == PROF_N, "PROF_NAMES and the P_* indices disagree");
 
 }  // namespace taiga
 
@@ -1822,6 +1825,39 @@ int tg_lookup_product_probe(tg_ctx* ctx, uint32_t k, uint64_t u, const uint8_t* 
   std::vector<GpSeg> segs{GpSeg{(long)u, d_z.p, false, fd_one_mont<FpCfg>()}};
   if ((rc = dev_gp_scan(c, dd.pd, d_num.p, d_den.p, segs))) return rc;
   return diag_download(c, d_z.p, u + 1, z_out, "lookup probe");
+}
+
+int tg_lookup_permute_probe(tg_ctx* ctx, uint64_t u, const uint8_t* a, const uint8_t* s,
+                            uint8_t* ap_out, uint8_t* sp_out) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || tg_enter(c)) return TG_ERR_BADARG;
+  if (!u || u > (uint64_t)LK_MAX_U) return TG_ERR_BADARG;
+  std::vector<Fp> ha, hs;
+  if (!diag_to_mont(a, u, ha) || !diag_to_mont(s, u, hs)) return TG_ERR_ENCODING;
+  // the prover sorts in slots of n = 2^k rows; here the network's own size
+  const size_t np = (size_t)lk_padded((long)u);
+  DevTmp<Fp> d_a, d_s, d_ap, d_t, d_sp;
+  hipError_t e = diag_upload(c, d_a, ha);
+  if (e == hipSuccess) e = diag_upload(c, d_s, hs);
+  if (e == hipSuccess) e = d_ap.alloc(np);
+  if (e == hipSuccess) e = d_t.alloc(np);
+  if (e == hipSuccess) e = d_sp.alloc(u);
+  if (e != hipSuccess) return set_err(c, "permute probe upload", e);
+  const Fp* src[2] = {d_a.p, d_s.p};
+  Fp* dst[2] = {d_ap.p, d_t.p};
+  Fp *pap = d_ap.p, *psp = d_sp.p;
+  const Fp* pt = d_t.p;
+  DiagDev dd;
+  int rc = dev_lk_sort(c, 2, src, dst, (long)u, (long)np);
+  if (!rc) rc = dev_lk_permute(c, dd.pd, 1, &pap, &pt, &psp, (long)u);
+  if (rc) return rc;
+  dev_lk_fetch_err(c, dd.pd);
+  e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return set_err(c, "permute probe", e);
+  if (dd.pd.lk_err_h) return TG_ERR_BADARG;  // an element of a is missing from s
+  rc = diag_download(c, d_ap.p, u, ap_out, "permute probe");
+  if (rc) return rc;
+  return diag_download(c, d_sp.p, u, sp_out, "permute probe");
 }
 
 }  /* extern "C" */
